@@ -7,6 +7,14 @@ RCCL all-reduce of the loss scalars when N > 1), with inputs already resident in
 Metric (BASELINE.json): log-density evaluations counted as samples·steps per second.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg1|cfg2|cfg2p|cfg3|cfg4|cfg4r|cfg5|nv20] [--mode infer|grad]
+                  [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set-up, warm-up and pre-roll, K timed steps, the JSON line.  `--full` adds what the
+line carried besides the headline (the `secondary`, `secondary_bf16x6`, `secondaries`, `small_batch` and `cpu_baseline`
+measurements below).  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (rank 0): `loss`
+(float64, 0-dim) and, for --mode infer, `logp` (B,) and `regs` (3, B) of the inference call, for --mode grad `gradient`
+(nparams,), all float32; more than 64 MB of them are cut to a fixed, seeded sample of columns.  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ...`;
 the batch columns are sharded by rank (weak scaling: 65 536 columns per GPU), no data-path
@@ -28,13 +36,13 @@ the same steady state, and `roofline.frac` = flop_per_launch / (CSV average) rep
 The JSON line also carries
   roofline     — the fused solve kernel against the f32 MFMA peak (the path is compute-bound:
                  ≥ 97 flop/B); its HBM figure is reported beside it.
-  secondary    — the north_star's target configuration (cfg2p: the same flow under Tsit5 x 40)
+  secondary    — (--full) the north_star's target configuration (cfg2p: the same flow under Tsit5 x 40)
                  measured by the same protocol in the same process, with its own roofline.
-  secondaries  — (default one-GPU line only) every other BASELINE configuration, the loss + gradient of cfg2, cfg3 and cfg4 and the
-                 reference's default architecture at nvariables = 20 (inference and loss + gradient), compactly, same protocol.
-  small_batch  — (default one-GPU line only) wall time of one call at the reference's own batch size, host side included: its
+  secondaries  — (--full, default one-GPU line only) every other BASELINE configuration, the loss + gradient of cfg2, cfg3 and cfg4
+                 and the reference's default architecture at nvariables = 20 (inference and loss + gradient), compactly, same protocol.
+  small_batch  — (--full, default one-GPU line only) wall time of one call at the reference's own batch size, host side included: its
                  PkgBenchmark scenario (ICNF(nvariables = 1), VCABM, 2^10 samples; `loss` in TrainMode and TestMode) and cfg1.
-  cpu_baseline — CPU fp32 restatements of the same algorithm on this host's cores (rank 0, N = 1):
+  cpu_baseline — (--full) CPU fp32 restatements of the same algorithm on this host's cores (rank 0, N = 1):
                  the C port (oracle/cnf_oracle.c, cache-blocked register-tiled products, AVX-512 when
                  the CPU has it) and a whole-batch BLAS leg (torch.mm on every host thread at the full
                  batch — the structure of the reference's CPU path); `value` is the faster one.
@@ -202,14 +210,19 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--preroll-seconds", type=float, default=2.0,
                     help="untimed back-to-back launches before the timed steps so the clock has settled (0 = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: the 'auto' secondaries below, the small-batch latencies "
+                         "and the CPU baseline (off by default: a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--secondary", default="auto",
                     help="second workload measured by the same protocol and reported under 'secondary' "
-                         "(auto = cfg2p, the north_star's Tsit5 target, when --config cfg2 --mode infer; none = off)")
+                         "(auto = cfg2p, the north_star's Tsit5 target, when --full --config cfg2 --mode infer; none = off)")
     ap.add_argument("--secondaries", default="auto",
                     help="further workloads measured by the same protocol in the same process and reported compactly under "
                          "'secondaries' ({value, ms_per_step, roofline: {kernel_ms, frac}, loss}): a comma list of "
                          "name[:grad] (e.g. cfg3,cfg4,cfg5,cfg2:grad,cfg4:grad,nv20,nv20:grad), 'none', or 'auto' = exactly that list on the "
-                         "default one-GPU cfg2 line, so that every BASELINE configuration and the gradient are on the driver-run line")
+                         "default one-GPU cfg2 line with --full, so that every BASELINE configuration and the gradient are on that line")
     ap.add_argument("--mode", default="infer", choices=["infer", "grad"],
                     help="infer: loss (default, the BASELINE metric); grad: loss_and_gradient — forward with "
                          "checkpoints + reverse sweep + all-reduce of nparams floats")
@@ -221,7 +234,7 @@ def parse():
                          "'torch' = torch.distributed all_reduce")
     ap.add_argument("--bf16x6-secondary", default="auto", choices=["auto", "on", "off"],
                     help="also measure the opt-in split-bf16 arithmetic of the same workload and report it as 'secondary_bf16x6' "
-                         "with its own error against the fp64 oracle (auto: the default cfg2 line on one GPU)")
+                         "with its own error against the fp64 oracle (auto: the default cfg2 line on one GPU with --full)")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the N > 1 code path (process group, RCCL communicator, loss all-reduce inside the timed "
                          "loop, teardown) even with one rank: the rehearsal of a multi-GPU launch on a 1-GPU box")
@@ -229,7 +242,10 @@ def parse():
                     help="seconds to wait for ncclCommInitRank of the library's communicator before giving up (exit 3)")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; gloo for "
                     "the single-GPU launch-contract test, where all ranks share device 0)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -433,7 +449,7 @@ def _quarters(ms):
     return float(np.mean(ms[:q])), float(np.mean(ms[-q:])), float(np.median(ms))
 
 
-def measure(w, a, steps, warmup, preroll_s, pkg, torch, dist, world, dev, probe):
+def measure(w, a, steps, warmup, preroll_s, pkg, torch, dist, world, dev, probe, keep_outputs=False):
     """Warm-up, pre-roll to the sustained clock, then exactly `steps` timed steps.  Returns timings.
     `sharded` (N > 1, or --force-dist with one rank) selects the column-shard form of the step: cnf_loss_sums + the
     all-reduce of the loss scalars instead of cnf_loss_mean, and the barrier / max-over-ranks timing."""
@@ -442,19 +458,23 @@ def measure(w, a, steps, warmup, preroll_s, pkg, torch, dist, world, dev, probe)
     sharded = world > 1 or a.force_dist
     state = {}
 
-    def launch(ev=None):
+    def launch(ev=None, keep=False):
         """One step; the event pair brackets the dominant kernel's launch (the solve; for --mode grad the
-        whole loss + gradient) on the launching stream."""
+        whole loss + gradient) on the launching stream.  `keep`: hold on to what the step returned (--dump-outputs)."""
         if ev is not None:
             ev[0].record()
         if grad:
-            state["loss"], _ = pkg.loss_and_gradient(icnf, mode, *args, eps=E)
+            state["loss"], g = pkg.loss_and_gradient(icnf, mode, *args, eps=E)
             if ev is not None:
                 ev[1].record()
+            if keep:
+                state["outputs"] = {"gradient": g}
             return
         logp, regs = pkg.inference(icnf, mode, *args, eps=E, _raw=True)
         if ev is not None:
             ev[1].record()
+        if keep:
+            state["outputs"] = {"logp": logp, "regs": regs}
         if not sharded:    # one process: the mean comes out of the library's two reduction kernels (cnf_loss_mean), as in pkg.loss
             state["loss"] = pkg.loss_mean(icnf, mode, logp, regs)
         else:
@@ -504,7 +524,7 @@ def measure(w, a, steps, warmup, preroll_s, pkg, torch, dist, world, dev, probe)
     # ---- the timed region: exactly `steps` steps ----
     t0 = time.perf_counter()
     for i in range(steps):
-        launch(ev[i])
+        launch(ev[i], keep=keep_outputs and i == steps - 1)
     sync()
     elapsed = time.perf_counter() - t0
     if sharded:
@@ -527,7 +547,32 @@ def measure(w, a, steps, warmup, preroll_s, pkg, torch, dist, world, dev, probe)
     mhz_end = probe.drain()
     return dict(elapsed=elapsed, kern_ms=float(np.mean(ms)), kern_ms_median=float(np.median(ms)),
                 kern_ms_min=float(np.min(ms)), kern_ms_max=float(np.max(ms)), sustained=sustained,
-                clock_mhz_after_timed=(mhz_end[0] if mhz_end else None), loss=float(state["loss"]))
+                clock_mhz_after_timed=(mhz_end[0] if mhz_end else None), loss=float(state["loss"]),
+                outputs=dict(state["outputs"], loss=state["loss"]) if keep_outputs else None)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, d, B):
+    """What the last timed step returned, as d/<name>.npy: the loss in float64, the arrays in float32.  The per-sample arrays (logp,
+    regs: last axis = the B columns) are cut to one fixed, seeded sample of columns when all together would exceed DUMP_LIMIT_BYTES."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    for k, v in outputs.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        arrs[k] = a.astype(np.float64 if k == "loss" else np.float32)
+    per_sample = [k for k in ("logp", "regs") if k in arrs]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES and per_sample:
+        per_col = sum(arrs[k].nbytes // B for k in per_sample)
+        fixed = total - per_col * B
+        keep = np.sort(np.random.default_rng(0).choice(B, size=max(1, (DUMP_LIMIT_BYTES - fixed) // per_col), replace=False))
+        for k in per_sample:
+            arrs[k] = arrs[k][..., keep]
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return sorted(arrs)
 
 
 def report(w, m, a, steps, warmup, world):
@@ -692,8 +737,13 @@ def main():
 
     w = make_workload(pkg, o64, a.config, a, rank, dev, torch)
     w["collective"] = collective
-    m = measure(w, a, a.steps, a.warmup, a.preroll_seconds, pkg, torch, dist, world, dev, probe)
-    sec_name = ("cfg2p" if (a.config == "cfg2" and a.mode == "infer" and not a.batch) else "none") \
+    m = measure(w, a, a.steps, a.warmup, a.preroll_seconds, pkg, torch, dist, world, dev, probe, keep_outputs=bool(a.dump_outputs))
+    outputs = m.pop("outputs")
+    if outputs is not None and rank == 0:
+        names = dump_outputs(outputs, a.dump_outputs, w["B"])
+        print(f"bench.py: the last timed step's {', '.join(names)} written to {a.dump_outputs}", file=sys.stderr, flush=True)
+    outputs = None
+    sec_name = ("cfg2p" if (a.full and a.config == "cfg2" and a.mode == "infer" and not a.batch) else "none") \
         if a.secondary == "auto" else a.secondary
     sec = None
     if sec_name != "none":
@@ -704,7 +754,7 @@ def main():
 
     # the opt-in split-bf16 arithmetic as a reported secondary (never the headline: exact f32 is the validated path)
     bf = None
-    want_bf = a.bf16x6_secondary == "on" or (a.bf16x6_secondary == "auto" and a.config in ("cfg2", "cfg3") and a.mode == "infer" and
+    want_bf = a.bf16x6_secondary == "on" or (a.bf16x6_secondary == "auto" and a.full and a.config in ("cfg2", "cfg3") and a.mode == "infer" and
                                               a.arith == "f32" and world == 1 and not a.force_dist and not a.batch)
     if want_bf:
         try:
@@ -724,7 +774,8 @@ def main():
     # long ones), compactly: VERDICT r3 #1 - cfg3 / cfg4 / cfg5 and the gradient figures were builder-run claims only
     default_line = (a.config == "cfg2" and a.mode == "infer" and a.arith == "f32" and world == 1 and not a.force_dist and
                     not a.batch and a.path == 0)
-    sec_list = ("cfg3,cfg4,cfg5,cfg2:grad,cfg3:grad,cfg4:grad,nv20,nv20:grad" if default_line else "none") if a.secondaries == "auto" else a.secondaries
+    sec_list = ("cfg3,cfg4,cfg5,cfg2:grad,cfg3:grad,cfg4:grad,nv20,nv20:grad" if default_line and a.full else "none") \
+        if a.secondaries == "auto" else a.secondaries
     more = []
     if sec_list != "none":
         for item in [x.strip() for x in sec_list.split(",") if x.strip()]:
@@ -743,7 +794,7 @@ def main():
                 torch.cuda.empty_cache()
 
     small = None
-    if default_line and a.secondaries == "auto":
+    if default_line and a.secondaries == "auto" and a.full:
         try:
             small = small_batch_latency(pkg, o64, a, dev, torch)
         except Exception as ex:  # pragma: no cover
@@ -831,7 +882,7 @@ def main():
             detail["secondary_bf16x6"] = r3
         elif bf is not None:
             out["secondary_bf16x6"] = {"error": bf[1]}
-        if world == 1 and not a.no_cpu_baseline and not a.force_dist:
+        if world == 1 and a.full and not a.no_cpu_baseline and not a.force_dist:
             p, xs, eps, ys = w["host"]
             cb = cpu_baseline(o64, oc, w["spec"], w["alg"], p, xs, eps, ys, a.cpu_seconds)
             detail["cpu_baseline"] = cb

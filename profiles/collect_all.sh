@@ -7,8 +7,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err
-for c in cfg1 cfg3 cfg4 cfg5; do python bench.py --config $c --steps 40 --no-cpu-baseline > $OUT/${TAG}_bench_$c.json 2>/dev/null; done
+python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err
+for c in cfg1 cfg3 cfg4 cfg5; do python bench.py --full --config $c --steps 40 --no-cpu-baseline > $OUT/${TAG}_bench_$c.json 2>/dev/null; done
 for c in cfg2 cfg3 cfg4 nv20; do python bench.py --config $c --mode grad --steps 10 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_${c}_grad.json 2>/dev/null; done
 for c in cfg2 cfg2p cfg3 cfg4 cfg5; do
   bash profiles/collect.sh $TAG $c > $OUT/collect_$c.log 2>&1

@@ -3,7 +3,7 @@ Tsit5 x 40.  These shapes keep their per-wave forward plan (the one-launch adapt
 gradient runs on the cooperative reverse sweep through an auxiliary cooperative plan + image (cnf_handle::plan_cg):
 86.4 / 105.9 ms on the slab-accumulator kernel (CNF_COOP_GRAD_MID=0) -> 77.3 / 79.8 ms."""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as entry
 pkg = entry.load_package()
 dev = torch.device("cuda:0")
