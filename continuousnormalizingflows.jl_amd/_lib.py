@@ -18,6 +18,7 @@ MAX_LAYERS = 8
 
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_NO_PARAMS, ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 ACT_IDENTITY, ACT_TANH, ACT_SOFTPLUS = 0, 1, 2
+ACT_SIGMOID, ACT_SWISH, ACT_ELU, ACT_GELU = 4, 5, 6, 7   # (3 is reserved)
 MODE_HUTCH_VJP, MODE_HUTCH_JVP, MODE_EXACT = 0, 1, 2
 ALG_RK4, ALG_TSIT5 = 0, 1
 ALG_VCABM = 2   # CNF_ALG_VCABM: taken by cnf_loss_adaptive only - the multistep solve has its own entry points (cnf_vcabm_*, cnf_solve_vcabm)

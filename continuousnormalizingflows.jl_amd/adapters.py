@@ -213,7 +213,7 @@ class CondICNFDist(ICNFDist):
 # MLJBase.save(file, mach) / machine(file) (examples/usage.jl:96-98): the fitted model as one file
 # ---------------------------------------------------------------------------------------------------------------
 _ALG_NAMES = {"VCABM": _icnf.VCABM, "Tsit5": _icnf.Tsit5, "RK4": _icnf.RK4}
-_ACT_NAMES = {_icnf._lib.ACT_IDENTITY: "identity", _icnf._lib.ACT_TANH: "tanh", _icnf._lib.ACT_SOFTPLUS: "softplus"}
+_ACT_NAMES = _icnf._ACT_NAMES   # every activation id -> the name Dense maps back to it
 
 
 def save_machine(path: str, model: _MLJICNF, fitresult) -> None:

@@ -55,6 +55,8 @@ inline Tableau make_tableau(int alg) {
 //   softplus : NNlib.softplus(a) = log1p(exp(-|a|)) + relu(a);  d = sigmoid(a)
 // Built from v_exp_f32 / v_log_f32 / v_rcp_f32 (about 1 ulp each); absolute error of h and d
 // is <= 2e-7, checked against the fp64 oracle in tests/test_parity_gpu.py.
+// The layer-wise and SIMT paths also take sigmoid, swish, ELU and GELU (act_fwd_rt below); the fused
+// kernels are instantiated for tanh and softplus only.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
@@ -94,11 +96,102 @@ __device__ __forceinline__ float act_fwd(float a, float& d) {
     }
 }
 
-__device__ __forceinline__ float act_fwd_rt(int act, float a, float& d) {
+// sigmoid(x) and 1 - sigmoid(x) from e = exp(-|x|) in (0, 1]: neither overflows, and the smaller of the two keeps its
+// relative accuracy (1 - s is not formed by cancellation)
+__device__ __forceinline__ void sigmoid_pair(float x, float& s, float& c) {
+    const float e = fast_exp(-fabsf(x));
+    const float r = fast_rcp(1.f + e);
+    const float p = e * r;
+    s = x >= 0.f ? r : p;
+    c = x >= 0.f ? p : r;
+}
+constexpr float kGeluK0 = 0.7978845608028654f;    // sqrt(2 / pi)
+constexpr float kGeluK1 = 0.035677408136300125f;  // sqrt(2 / pi) * 0.044715
+// a with |a| clamped to 1e4 (a NaN passes through): past |a| ~ 10, sigmoid(2u) is exactly 0 or 1, so nothing but the overflow changes
+__device__ __forceinline__ float gelu_tail(float a) { return fabsf(a) > 1e4f ? copysignf(1e4f, a) : a; }
+
+// sigmoid : h = s = 1/(1+exp(-a));            d = s (1 - s)
+// swish   : h = a s;                          d = s + h (1 - s)                     (NNlib.swish, SiLU)
+// ELU     : h = a (a >= 0), exp(a) - 1;       d = 1 (a >= 0), exp(a)                (NNlib.elu, alpha = 1)
+// GELU    : h = a sigmoid(2u), u = sqrt(2/pi) (a + 0.044715 a^3) = a/2 (1 + tanh u);
+//           d = s + 2 a s (1 - s) u'                                                 (NNlib.gelu, tanh form)
+// Every form, act_dd_rt below included, is free of NaN for every finite a: exp only ever sees a non-positive argument, and the
+// products that meet a large |a| meet an s (1 - s) that underflows to 0 first (swish at a = -90 gives h = -0).  GELU's u' and
+// a u'^2 would overflow first (a u'^2 near |a| ~ 1e8): their a is clamped to +-1e4 (gelu_tail), where s (1 - s) is already 0.
+// identity / tanh / softplus: the activations of the fused kernels (the layer-wise instances built for them run this)
+__device__ __forceinline__ float act_fwd_rt3(int act, float a, float& d) {
     if (act == CNF_ACT_TANH) return act_fwd<CNF_ACT_TANH>(a, d);
     if (act == CNF_ACT_SOFTPLUS) return act_fwd<CNF_ACT_SOFTPLUS>(a, d);
     d = 1.f;
     return a;
+}
+
+// every id of cnf.h
+__device__ __forceinline__ float act_fwd_rt(int act, float a, float& d) {
+    if (act == CNF_ACT_SIGMOID) {
+        float s, c;
+        sigmoid_pair(a, s, c);
+        d = s * c;
+        return s;
+    }
+    if (act == CNF_ACT_SWISH) {
+        float s, c;
+        sigmoid_pair(a, s, c);
+        const float h = a * s;
+        d = fmaf(h, c, s);
+        return h;
+    }
+    if (act == CNF_ACT_ELU) {
+        const float e = fast_exp(fminf(a, 0.f));
+        // exp(a) - 1 cancels near 0: the cubic Taylor form below |a| = 2^-5 (error < a^4 / 24 = 4e-8), so h < 0 for every a < 0
+        const float em1 = fabsf(a) < 0.03125f ? a * fmaf(a, fmaf(a, 0.16666667f, 0.5f), 1.f) : e - 1.f;
+        d = a >= 0.f ? 1.f : e;
+        return a >= 0.f ? a : em1;
+    }
+    if (act == CNF_ACT_GELU) {
+        const float t = gelu_tail(a), t2 = t * t;
+        float s, c;
+        sigmoid_pair(2.f * t * fmaf(kGeluK1, t2, kGeluK0), s, c);
+        const float du = fmaf(3.f * kGeluK1, t2, kGeluK0);          // u'
+        d = fmaf(2.f * t * s * c, du, s);
+        return a * s;
+    }
+    return act_fwd_rt3(act, a, d);
+}
+
+// act''(a) of every activation id, from x and d = act'(a): x is h = act(a) for tanh, sigmoid and ELU, the pre-activation a for
+// swish and GELU (act_dd_needs_pre: their act'' is not a function of (h, act')), unused for identity and softplus.
+// An id outside the enum gives NaN, never a silent 0 (the host checks the ids before every launch as well).
+__host__ __device__ constexpr bool act_dd_needs_pre(int act) { return act == CNF_ACT_SWISH || act == CNF_ACT_GELU; }
+__host__ __device__ constexpr bool act_dd_reads_x(int act) {
+    return act == CNF_ACT_TANH || act == CNF_ACT_SIGMOID || act == CNF_ACT_ELU || act_dd_needs_pre(act);
+}
+__host__ __device__ constexpr bool act_id_valid(int act) {
+    return act == CNF_ACT_IDENTITY || act == CNF_ACT_TANH || act == CNF_ACT_SOFTPLUS || act == CNF_ACT_SIGMOID ||
+           act == CNF_ACT_SWISH || act == CNF_ACT_ELU || act == CNF_ACT_GELU;
+}
+__device__ __forceinline__ float act_dd_rt(int act, float x, float d) {
+    switch (act) {
+        case CNF_ACT_IDENTITY: return 0.f;
+        case CNF_ACT_TANH: return -2.f * x * d;                        // -2 h act'
+        case CNF_ACT_SOFTPLUS: return d * (1.f - d);                   // act' (1 - act')
+        case CNF_ACT_SIGMOID: return d * (1.f - 2.f * x);              // act' (1 - 2 h)
+        case CNF_ACT_ELU: return x < 0.f ? d : 0.f;                    // exp(a) below 0
+        case CNF_ACT_SWISH: {                                          // s (1 - s) (2 + a (1 - 2 s))
+            float s, c;
+            sigmoid_pair(x, s, c);
+            return s * c * fmaf(x, c - s, 2.f);
+        }
+        case CNF_ACT_GELU: {                                           // 2 s (1 - s) (2 u' + a (2 u'^2 (1 - 2 s) + u''))
+            const float t = gelu_tail(x), t2 = t * t;
+            float s, c;
+            sigmoid_pair(2.f * t * fmaf(kGeluK1, t2, kGeluK0), s, c);
+            const float du = fmaf(3.f * kGeluK1, t2, kGeluK0);
+            const float inner = fmaf(2.f * du * du, c - s, 6.f * kGeluK1 * t);
+            return 2.f * s * c * fmaf(t, inner, 2.f * du);
+        }
+        default: return __builtin_nanf("");
+    }
 }
 
 constexpr float kLog2Pi = 1.8378770664093453f;

@@ -26,6 +26,12 @@
 // batched GEMMs over column chunks, each chunk accumulating (beta = 1) into its own slab for the whole
 // solve; one kernel sums the slabs in a fixed order at the end (no atomics: bit-reproducible).
 //
+// Activations: every id of cnf.h.  The reverse sweep needs act''_l: tanh, softplus, sigmoid and ELU rebuild it from a_l and
+// act'_l (act_dd_rt, cnf_common.h); swish and GELU cannot, so the forward chain of the gradient also writes the pre-activations
+// z_l of those layers (ACT epilogue) and act'' is recomputed from z_l.  Extra bytes: 4 H_l B per swish / GELU layer - in the
+// recomputing mode once (one stage's worth), in the keep-activations mode per kept stage (4 H_l B x stages x steps, counted
+// in the CNF_LAYERED_ACT_GIB budget).  Chains of identity / tanh / softplus keep exactly the workspace they had.
+//
 // The products run on the hand-written MFMA kernels of cnf_lgemm.hip (weights pre-packed into operand images once per parameter
 // set; activation / act' / the pullback's elementwise product fused into their epilogues); the library has no dependency on a
 // vendor BLAS.
@@ -48,7 +54,7 @@ size_t lg_image_floats(int M, int K);
 bool lg_gemm_supported(int M, int K);
 hipError_t lg_gemm(const float* img, int M, int K, const float* in, int ldb, float* out, int ldc, long long N, int epi,
                    const float* e, int lde, float* dout, int ldd, int act, hipStream_t st, const float* e2 = nullptr,
-                   const float* a3 = nullptr, int ld3 = 0, int first = 0);
+                   const float* a3 = nullptr, int ld3 = 0, int first = 0, float* pre = nullptr);
 bool lg_wgrad_supported(int M, int Nc);
 int lg_wgrad_chunks(int M, long long B, int num_cus, long long* chunk_out, int per_cu_dflt = 2, int Nc = 0);
 hipError_t lg_wgrad(float* slabs, long long slab_stride, long long chunk, int nchunks, int M, int Nc, const float* x, int ldx,
@@ -283,17 +289,16 @@ __global__ void bottom_kernel(const float* __restrict__ db, const float* __restr
     acc2[i] = first ? x * v[i] : fmaf(x, v[i], acc2[i]);   // the first probe initialises the sum
 }
 
-// sbar = abar .* act' + acc2 .* act''   (tanh: act'' = -2 a act';  softplus: act'' = act' (1 - act'))
+// sbar = abar .* act' + acc2 .* act''   (act'' = act_dd_rt(act, x, act'): x the activations a (ld H + 1; tanh: act'' = -2 a act'),
+// or the pre-activations (ld H) of swish / GELU)
 __global__ void sbar_kernel(float* __restrict__ sbar, const float* __restrict__ abar, const float* __restrict__ d,
-                            const float* __restrict__ acc2, const float* __restrict__ a, int act, int H, long long B) {
+                            const float* __restrict__ acc2, const float* __restrict__ x, int ldx, int act, int H, long long B) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)H * B) return;
     const long long j = i / H;
     const int f = (int)(i % H);
     const float dd = d[i];
-    float e = 0.f;
-    if (act == CNF_ACT_TANH) e = -2.f * a[j * (H + 1) + f] * dd;
-    else if (act == CNF_ACT_SOFTPLUS) e = dd * (1.f - dd);
+    const float e = act_dd_rt(act, act_dd_reads_x(act) ? x[j * ldx + f] : 0.f, dd);
     sbar[i] = fmaf(acc2[i], e, abar[i] * dd);
 }
 
@@ -516,13 +521,13 @@ enum { OPN = 0, OPT = 1 };
 static hipError_t lg_product(LayeredGrad& G, const float* PA, int ta, int m, long long n, int k, const float* A, int lda,
                              const float* Bm, int ldb, float* Cm, int ldc, int epi, const float* e, int lde, float* dout, int ldd,
                              int act, hipStream_t st, const float* e2 = nullptr, const float* a3 = nullptr, int ld3 = 0,
-                             int first = 0) {
+                             int first = 0, float* pre = nullptr) {
     if (!lg_gemm_supported(m, k)) return hipErrorNotSupported;
     const float* img = nullptr;
     const long long rel = A - PA;
     hipError_t er = ta == OPN ? lg_image(G, PA, rel, 1, lda, m, k, &img, st) : lg_image(G, PA, rel, lda, 1, m, k, &img, st);
     if (er != hipSuccess) return er;
-    return lg_gemm(img, m, k, Bm, ldb, Cm, ldc, n, epi, e, lde, dout, ldd, act, st, e2, a3, ld3, first);
+    return lg_gemm(img, m, k, Bm, ldb, Cm, ldc, n, epi, e, lde, dout, ldd, act, st, e2, a3, ld3, first, pre);
 }
 
 // du = augmented_f(u + dt sum coef k, p, t): forward chain, then the trace estimator of the handle's mode
@@ -533,6 +538,11 @@ hipError_t layered_aug_f(LayeredGrad** ctx, const cnf_config& c, const float* P_
         *err = "layered evaluation: a layer is wider than the product kernels cover (512 outputs, 639 inputs)";
         return hipErrorNotSupported;
     }
+    for (int l = 0; l < c.n_layers; ++l)
+        if (!act_id_valid(c.acts[l])) {
+            *err = "layered evaluation: unknown activation id";
+            return hipErrorInvalidValue;
+        }
     if (!*ctx) *ctx = new LayeredGrad();
     LayeredGrad& G = **ctx;
     const int N = c.n_layers, D = c.nvars + c.naug, C = c.ncond, S = D + 3;
@@ -660,6 +670,11 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
         *err = "layered gradient: a layer is wider than the product kernels cover (512 outputs, 639 inputs)";
         return hipErrorNotSupported;
     }
+    for (int l = 0; l < c.n_layers; ++l)
+        if (!act_id_valid(c.acts[l])) {   // (act_dd_rt has no act'' for it)
+            *err = "layered gradient: unknown activation id";
+            return hipErrorInvalidValue;
+        }
     if (!*ctx) *ctx = new LayeredGrad();
     LayeredGrad& G = **ctx;
     if (G.num_cus == 0) {
@@ -703,9 +718,14 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     const long long o_kck = keep_k ? take(DB * nst * nsteps) : 0;
     // the activations of every stage (a_l with its ones row, act'_l) are kept too when they fit the budget (default 48 GiB of
     // the 288; CNF_LAYERED_ACT_GIB): the reverse sweep then reads them instead of recomputing the forward chain of the stage
+    // (swish / GELU layers keep their pre-activations z_l as well: act'' is not a function of a_l and act'_l there)
     long long act_stage = (long long)(c.widths[0] + 1) * B;
-    for (int l = 0; l < N; ++l) act_stage += (long long)(L.wout[l] + 1) * B + (long long)L.wout[l] * B;
-    act_stage = (act_stage + 63) / 64 * 64 + 64 * (N + 2) * 2;
+    int npre = 0;
+    for (int l = 0; l < N; ++l) {
+        act_stage += (long long)(L.wout[l] + 1) * B + (long long)L.wout[l] * B;
+        if (act_dd_needs_pre(L.act[l])) { act_stage += (long long)L.wout[l] * B; ++npre; }
+    }
+    act_stage = (act_stage + 63) / 64 * 64 + 64 * (N + 2) * 2 + 64 * npre;
     const double act_gib = (double)tuning().layered_act_gib;
     bool keep_act = keep_k && (double)act_stage * nst * nsteps * sizeof(float) <= act_gib * 1024.0 * 1024.0 * 1024.0;
     if (keep_act) {   // ... and half of what the device has free (counting the workspace this context already holds)
@@ -729,6 +749,8 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     }
     const long long WB = (long long)maxw * B;
     const long long o_t0 = take(WB), o_t1 = take(WB), o_t2 = take(WB), o_t3 = take(WB), o_t4 = take(WB);
+    long long o_z[CNF_MAX_LAYERS];   // pre-activations of the swish / GELU layers (recomputing mode; nothing for other layers)
+    for (int l = 0; l < N; ++l) o_z[l] = act_dd_needs_pre(L.act[l]) && !keep_act ? take((long long)L.wout[l] * B) : -1;
     if ((size_t)off > G.ws_floats) {
         if (G.ws) LG_HIP(hipFree(G.ws));
         G.ws = nullptr; G.ws_floats = 0;
@@ -742,12 +764,17 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     for (int j = 0; j < 6; ++j) { kz[j] = W + o_kz[j]; Zb[j] = W + o_zb[j]; }
     for (int l = 0; l <= N; ++l) a[l] = W + o_a[l];
     for (int l = 0; l < N; ++l) { d[l] = W + o_d[l]; v[l] = W + o_v[l]; acc2[l] = W + o_acc2[l]; dl[l] = W + o_dl[l]; }
-    // where stage s (= step * ns + stage) keeps its activations: a[] / d[] are pointed there before the stage's forward chain
+    float* z[CNF_MAX_LAYERS];
+    for (int l = 0; l < N; ++l) z[l] = o_z[l] >= 0 ? W + o_z[l] : nullptr;
+    // where stage s (= step * ns + stage) keeps its activations: a[] / d[] (/ z[]) are pointed there before the stage's forward chain
     auto point_act = [&](long long stage) {
         float* q = W + o_actck + stage * act_stage;
         auto grab = [&](long long nfl) { float* r = q; q += (nfl + 63) / 64 * 64; return r; };
         a[0] = grab((long long)(c.widths[0] + 1) * B);
-        for (int l = 0; l < N; ++l) { a[l + 1] = grab((long long)(L.wout[l] + 1) * B); d[l] = grab((long long)L.wout[l] * B); }
+        for (int l = 0; l < N; ++l) {
+            a[l + 1] = grab((long long)(L.wout[l] + 1) * B); d[l] = grab((long long)L.wout[l] * B);
+            if (act_dd_needs_pre(L.act[l])) z[l] = grab((long long)L.wout[l] * B);
+        }
     };
     float *lamv = W + o_lam, *kbar = W + o_kbar, *zs = W + o_zs, *gk = W + o_g, *gbar = W + o_gbar, *vN = W + o_vN;
     float *tdb = W + o_t0, *tdb2 = W + o_t1, *tvb = W + o_t2, *tsb = W + o_t3, *tab = W + o_t4;
@@ -764,13 +791,14 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     auto wgrad = [&](int l, const float* X, int ldx, const float* Y, int ldy, int ncols) -> hipError_t {
         return lg_wgrad(slabs + L.pa_off[l], npa_pad, kc, nslab, L.wout[l], ncols, X, ldx, Y, ldy, B, st);
     };
-    // forward chain at (zs, t): a_l, act'_l for every layer; zdot = a_N
+    // forward chain at (zs, t): a_l, act'_l for every layer (and z_l for swish / GELU); zdot = a_N
     auto forward = [&](const float* zin, float t) -> hipError_t {
         hipLaunchKernelGGL(build_input_kernel, grid_for((long long)(c.widths[0] + 1) * B), dim3(TPB), 0, st, zin, t, ys, a[0],
                            D, C, c.autonomous, B);
         for (int l = 0; l < N; ++l) {
             hipError_t s = lg_product(G, PA, OPN, L.wout[l], B, L.win[l] + 1, PA + L.pa_off[l], L.wout[l], a[l], L.win[l] + 1,
-                                      a[l + 1], L.wout[l] + 1, LG_EPI_ACT, nullptr, 0, d[l], L.wout[l], L.act[l], st);
+                                      a[l + 1], L.wout[l] + 1, LG_EPI_ACT, nullptr, 0, d[l], L.wout[l], L.act[l], st, nullptr,
+                                      nullptr, 0, 0, z[l]);
             if (s != hipSuccess) return s;
         }
         return hipSuccess;
@@ -927,13 +955,15 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
             // top-down through the forward chain: sbar_l = abar_l .* act'_l + acc2_l .* act''_l (in the epilogue of the product
             // that makes abar_l), [Wbar_l | bbar_l] += sbar_l [a_{l-1}; 1]^T, abar_{l-1} = W_l^T sbar_l
             float *scur = tsb, *snxt = tab;
+            // (act'' from a_l, or from z_l for swish / GELU)
             hipLaunchKernelGGL(sbar_kernel, grid_for((long long)L.wout[N - 1] * B), dim3(TPB), 0, st, scur, kbar, d[N - 1], acc2[N - 1],
-                               a[N], L.act[N - 1], L.wout[N - 1], B);
+                               z[N - 1] ? z[N - 1] : a[N], z[N - 1] ? L.wout[N - 1] : L.wout[N - 1] + 1, L.act[N - 1], L.wout[N - 1], B);
             for (int l = N - 1; l >= 0; --l) {
                 LG_BLAS(wgrad(l, scur, L.wout[l], a[l], L.win[l] + 1, L.win[l] + 1));
                 if (l > 0) {
                     LG_BLAS(lg_product(G, PA, OPT, L.win[l], B, L.wout[l], PA + L.pa_off[l], L.wout[l], scur, L.wout[l], snxt, L.win[l],
-                                       LG_EPI_SBAR, d[l - 1], L.win[l], nullptr, 0, L.act[l - 1], st, acc2[l - 1], a[l], L.win[l] + 1, 0));
+                                       LG_EPI_SBAR, d[l - 1], L.win[l], nullptr, 0, L.act[l - 1], st, acc2[l - 1],
+                                       z[l - 1] ? z[l - 1] : a[l], z[l - 1] ? L.win[l] : L.win[l] + 1, 0));
                     float* tmp = scur; scur = snxt; snxt = tmp;
                 } else {
                     LG_BLAS(gemm(OPT, OPN, D, B, L.wout[0], PA, L.wout[0], scur, L.wout[0], Zb[i], D));   // Zbar_i = W_1[:,0:D]^T sbar_1

@@ -58,6 +58,13 @@ size_t lg_image_floats(int M, int K) { return (size_t)((M + 15) / 16) * ((K + 15
 //   BOTTOM  out = x .* e, dout (+)= x .* e2  (first: =)              (reverse of the pullback: vbar_l, acc2_l)
 //   SBAR    out = x .* e + e2 .* act''  (act'' from e = act' and the activations a3)   (reverse of the forward chain)
 enum { LG_EPI_PLAIN = 0, LG_EPI_ACT = 1, LG_EPI_MUL = 2, LG_EPI_MUL2 = 3, LG_EPI_BOTTOM = 4, LG_EPI_SBAR = 5 };
+// ACT and SBAR of sigmoid, swish, ELU and GELU are instances of their own (lg_gemm picks them by the activation id): the instances
+// of identity / tanh / softplus keep their code, registers and bits.  ACT_X also writes the pre-activation x to `pre` when it is
+// given (swish / GELU in the gradient's forward chain); SBAR_X takes act'' from act_dd_rt, a3 being the activations (sigmoid, ELU)
+// or those pre-activations (swish, GELU).
+enum { LG_EPI_ACT_X = 6, LG_EPI_SBAR_X = 7 };
+constexpr bool lg_epi_act(int epi) { return epi == LG_EPI_ACT || epi == LG_EPI_ACT_X; }
+constexpr bool lg_epi_sbar(int epi) { return epi == LG_EPI_SBAR || epi == LG_EPI_SBAR_X; }
 
 // four consecutive floats of a column whose stride (H + 1 for the arrays that carry a ones row) is not a multiple of four:
 // one 16-byte access with 4-byte alignment (gfx950 global memory accesses need dword alignment only)
@@ -75,6 +82,7 @@ struct LgGemmArgs {
     int M, K, MT, KQ, ldb, ldc, lde, ldd, ld3, act, first;
     int mts;               // M-tiles per workgroup row (blockIdx.y picks the group): wide outputs are split over several workgroups
     int spw;               // pipelined kernel: 32-sample sub-panels per workgroup
+    float* pre;            // ACT_X (may be null): the pre-activations x, [M x N] with column stride ldd
 };
 
 // MTW: 16-row tiles per wave (MT <= 4 MTW); NQ: 16-sample tiles per workgroup (each weight fragment feeds NQ sample tiles)
@@ -167,9 +175,22 @@ lg_gemm_kernel(LgGemmArgs a) {
             const bool full = r0 + 3 < a.M;
             if (EPI == LG_EPI_ACT) {
 #pragma unroll
+                for (int r = 0; r < 4; ++r) { float dd; v[r] = act_fwd_rt3(a.act, v[r], dd); dv[r] = dd; }
+            }
+            if (EPI == LG_EPI_ACT_X) {
+                if (a.pre) {
+                    float* pp = a.pre + col * (long long)a.ldd + r0;
+                    if (full) {
+                        *reinterpret_cast<f32x4u*>(pp) = f32x4u{v[0], v[1], v[2], v[3]};
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) if (r0 + r < a.M) pp[r] = v[r];
+                    }
+                }
+#pragma unroll
                 for (int r = 0; r < 4; ++r) { float dd; v[r] = act_fwd_rt(a.act, v[r], dd); dv[r] = dd; }
             }
-            if (EPI == LG_EPI_MUL || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM || EPI == LG_EPI_SBAR) {
+            if (EPI == LG_EPI_MUL || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM || lg_epi_sbar(EPI)) {
                 // elementwise operands of this lane's four rows (row-guarded scalar loads at the ragged edge)
                 auto load4 = [&](const float* base, int ld) -> f32x4 {
                     const float* p = base + col * (long long)ld + r0;
@@ -204,6 +225,11 @@ lg_gemm_kernel(LgGemmArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = fmaf(c2[r], e2v[r], v[r] * ev[r]);
                 }
+                if (EPI == LG_EPI_SBAR_X) {
+                    const f32x4 c2 = load4(a.e2, a.lde), av = load4(a.a3, a.ld3);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaf(c2[r], act_dd_rt(a.act, av[r], ev[r]), v[r] * ev[r]);
+                }
             }
             float* op = a.out + col * (long long)a.ldc + r0;
             if (full) {
@@ -212,7 +238,7 @@ lg_gemm_kernel(LgGemmArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (r0 + r < a.M) op[r] = v[r];
             }
-            if (EPI == LG_EPI_ACT || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM) {
+            if (lg_epi_act(EPI) || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM) {
                 float* dp = a.dout + col * (long long)a.ldd + r0;
                 if (full) {
                     *reinterpret_cast<f32x4u*>(dp) = f32x4u{dv[0], dv[1], dv[2], dv[3]};
@@ -222,7 +248,7 @@ lg_gemm_kernel(LgGemmArgs a) {
                 }
                 // the ones row behind the activations (row M of a column of ldc = M + 1 floats: the next product's bias rides on
                 // it), written by the lane that owns the last valid row
-                if (EPI == LG_EPI_ACT && a.ldc > a.M && r0 <= a.M - 1 && a.M - 1 < r0 + 4) a.out[col * (long long)a.ldc + a.M] = 1.f;
+                if (lg_epi_act(EPI) && a.ldc > a.M && r0 <= a.M - 1 && a.M - 1 < r0 + 4) a.out[col * (long long)a.ldc + a.M] = 1.f;
             }
         }
     }
@@ -239,9 +265,22 @@ __device__ __forceinline__ void lg_epilogue_tile(const LgGemmArgs& a, f32x4 v, i
     const bool full = r0 + 3 < a.M;
     if (EPI == LG_EPI_ACT) {
 #pragma unroll
+        for (int r = 0; r < 4; ++r) { float dd; v[r] = act_fwd_rt3(a.act, v[r], dd); dv[r] = dd; }
+    }
+    if (EPI == LG_EPI_ACT_X) {
+        if (a.pre) {
+            float* pp = a.pre + col * (long long)a.ldd + r0;
+            if (full) {
+                *reinterpret_cast<f32x4u*>(pp) = f32x4u{v[0], v[1], v[2], v[3]};
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) if (r0 + r < a.M) pp[r] = v[r];
+            }
+        }
+#pragma unroll
         for (int r = 0; r < 4; ++r) { float dd; v[r] = act_fwd_rt(a.act, v[r], dd); dv[r] = dd; }
     }
-    if (EPI == LG_EPI_MUL || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM || EPI == LG_EPI_SBAR) {
+    if (EPI == LG_EPI_MUL || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM || lg_epi_sbar(EPI)) {
         auto load4 = [&](const float* base, int ld) -> f32x4 {
             const float* p = base + col * (long long)ld + r0;
             if (full) { const f32x4u t = *reinterpret_cast<const f32x4u*>(p); return f32x4{t[0], t[1], t[2], t[3]}; }
@@ -275,6 +314,11 @@ __device__ __forceinline__ void lg_epilogue_tile(const LgGemmArgs& a, f32x4 v, i
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = fmaf(c2[r], e2v[r], v[r] * ev[r]);
         }
+        if (EPI == LG_EPI_SBAR_X) {
+            const f32x4 c2 = load4(a.e2, a.lde), av = load4(a.a3, a.ld3);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = fmaf(c2[r], act_dd_rt(a.act, av[r], ev[r]), v[r] * ev[r]);
+        }
     }
     float* op = a.out + col * (long long)a.ldc + r0;
     if (full) {
@@ -283,7 +327,7 @@ __device__ __forceinline__ void lg_epilogue_tile(const LgGemmArgs& a, f32x4 v, i
 #pragma unroll
         for (int r = 0; r < 4; ++r) if (r0 + r < a.M) op[r] = v[r];
     }
-    if (EPI == LG_EPI_ACT || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM) {
+    if (lg_epi_act(EPI) || EPI == LG_EPI_MUL2 || EPI == LG_EPI_BOTTOM) {
         float* dp = a.dout + col * (long long)a.ldd + r0;
         if (full) {
             *reinterpret_cast<f32x4u*>(dp) = f32x4u{dv[0], dv[1], dv[2], dv[3]};
@@ -291,7 +335,7 @@ __device__ __forceinline__ void lg_epilogue_tile(const LgGemmArgs& a, f32x4 v, i
 #pragma unroll
             for (int r = 0; r < 4; ++r) if (r0 + r < a.M) dp[r] = dv[r];
         }
-        if (EPI == LG_EPI_ACT && a.ldc > a.M && r0 <= a.M - 1 && a.M - 1 < r0 + 4) a.out[col * (long long)a.ldc + a.M] = 1.f;
+        if (lg_epi_act(EPI) && a.ldc > a.M && r0 <= a.M - 1 && a.M - 1 < r0 + 4) a.out[col * (long long)a.ldc + a.M] = 1.f;
     }
 }
 
@@ -498,14 +542,20 @@ static hipError_t lg_gemm_dispatch(LgGemmArgs a, hipStream_t st) {
 
 hipError_t lg_gemm(const float* img, int M, int K, const float* in, int ldb, float* out, int ldc, long long N, int epi,
                    const float* e, int lde, float* dout, int ldd, int act, hipStream_t st, const float* e2, const float* a3, int ld3,
-                   int first) {
+                   int first, float* pre) {
     if (N <= 0) return hipSuccess;
     LgGemmArgs a{};
-    a.img = img; a.in = in; a.out = out; a.e = e; a.dout = dout; a.e2 = e2; a.a3 = a3; a.N = N;
+    a.img = img; a.in = in; a.out = out; a.e = e; a.dout = dout; a.e2 = e2; a.a3 = a3; a.pre = pre; a.N = N;
     a.M = M; a.K = K; a.MT = (M + 15) / 16; a.KQ = (K + 15) / 16; a.ldb = ldb; a.ldc = ldc; a.lde = lde; a.ldd = ldd; a.ld3 = ld3;
     a.act = act; a.first = first;
+    if (!act_id_valid(act)) return hipErrorInvalidValue;
+    const bool fused_act = act == CNF_ACT_IDENTITY || act == CNF_ACT_TANH || act == CNF_ACT_SOFTPLUS;   // act_fwd_rt3's ids
+    if (epi == LG_EPI_ACT && !fused_act) epi = LG_EPI_ACT_X;
+    if (epi == LG_EPI_SBAR && !fused_act) epi = LG_EPI_SBAR_X;
     switch (epi) {
         case LG_EPI_ACT: return lg_gemm_dispatch<LG_EPI_ACT>(a, st);
+        case LG_EPI_ACT_X: return lg_gemm_dispatch<LG_EPI_ACT_X>(a, st);
+        case LG_EPI_SBAR_X: return lg_gemm_dispatch<LG_EPI_SBAR_X>(a, st);
         case LG_EPI_MUL: return lg_gemm_dispatch<LG_EPI_MUL>(a, st);
         case LG_EPI_MUL2: return lg_gemm_dispatch<LG_EPI_MUL2>(a, st);
         case LG_EPI_BOTTOM: return lg_gemm_dispatch<LG_EPI_BOTTOM>(a, st);

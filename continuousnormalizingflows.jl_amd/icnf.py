@@ -32,6 +32,7 @@ from .solvers import _adaptive_integrate, _solve_errors, _vcabm_integrate  # noq
 
 __all__ = [
     "ICNF", "TrainMode", "TestMode", "Dense", "Chain", "PlanarLayer", "tanh", "softplus", "identity",
+    "sigmoid", "swish", "elu", "gelu",
     "HIPVecJacMatrixMode", "HIPJacVecMatrixMode", "LuxVecJacMatrixMode", "LuxJacVecMatrixMode",
     "DIVecJacMatrixMode", "DIJacVecMatrixMode", "Tsit5", "RK4", "VCABM", "setup", "inference", "generate",
     "loss", "augmented_f", "loss_and_gradient",
@@ -103,9 +104,28 @@ def softplus(x):
     return torch.nn.functional.softplus(x)
 
 
-_ACT_IDS = {identity: _lib.ACT_IDENTITY, tanh: _lib.ACT_TANH, softplus: _lib.ACT_SOFTPLUS,
-            None: _lib.ACT_IDENTITY, "identity": _lib.ACT_IDENTITY, "tanh": _lib.ACT_TANH,
-            "softplus": _lib.ACT_SOFTPLUS}
+def sigmoid(x):
+    return torch.sigmoid(x)
+
+
+def swish(x):
+    return x * torch.sigmoid(x)
+
+
+def elu(x):
+    return torch.nn.functional.elu(x)
+
+
+def gelu(x):
+    return torch.nn.functional.gelu(x, approximate="tanh")
+
+
+# the module functions, one per activation id (include/cnf.h CNF_ACT_*); each id's canonical name is its function's name
+_ACT_FUNCS = {identity: _lib.ACT_IDENTITY, tanh: _lib.ACT_TANH, softplus: _lib.ACT_SOFTPLUS, sigmoid: _lib.ACT_SIGMOID,
+              swish: _lib.ACT_SWISH, elu: _lib.ACT_ELU, gelu: _lib.ACT_GELU}
+_ACT_NAMES = {i: f.__name__ for f, i in _ACT_FUNCS.items()}   # id -> name (the machine file stores names)
+_ACT_IDS = {**_ACT_FUNCS, **{n: i for i, n in _ACT_NAMES.items()}, None: _lib.ACT_IDENTITY,
+            torch.sigmoid: _lib.ACT_SIGMOID, torch.nn.functional.silu: _lib.ACT_SWISH, "silu": _lib.ACT_SWISH}
 
 
 @dataclass
@@ -121,7 +141,7 @@ class Dense:
             return _ACT_IDS[self.activation]
         except KeyError:
             raise TypeError(f"MethodError: no HIP kernel for activation {self.activation!r} "
-                            "(supported: identity, tanh, softplus)") from None
+                            "(supported: identity, tanh, softplus, sigmoid, swish, elu, gelu)") from None
 
 
 @dataclass
@@ -231,7 +251,9 @@ class ICNF:
         adaptive=False (and `dt` or `nsteps`): the whole solve is one fused launch.  VCABM() and Tsit5() with
         adaptive=True (OrdinaryDiffEq's default; reltol/abstol default 1e-4 as in the reference) step under the
         solver's controller on the host with one device attempt per step (`_vcabm_integrate`, `_adaptive_integrate`).
-      * `nn` must be a Chain of Dense layers with identity/tanh/softplus activations.
+      * `nn` must be a Chain of Dense layers with identity/tanh/softplus/sigmoid/swish/elu/gelu activations
+        (elu with alpha = 1, gelu in its tanh form).  Nets with sigmoid, swish, elu or gelu hidden layers run
+        layer-wise (or thread-per-sample for layers wider than 512): the fused kernels are built for tanh and softplus.
       * data_type is Float32.
     """
 

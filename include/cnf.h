@@ -59,8 +59,18 @@ typedef enum {
     CNF_ERR_COMM = -6          /* RCCL error, or librccl.so.1 could not be loaded (message in cnf_last_error) */
 } cnf_status;
 
-/* activation ids of Lux.Dense layers (src/core/icnf.jl:67-71) */
-enum { CNF_ACT_IDENTITY = 0, CNF_ACT_TANH = 1, CNF_ACT_SOFTPLUS = 2 };
+/* activation ids of Lux.Dense layers (src/core/icnf.jl:67-71).  Every kernel family takes identity, tanh and softplus; the
+ * fused (MFMA) kernels are built for tanh and softplus hidden layers only, so a chain with sigmoid, swish, ELU or GELU runs
+ * layer-wise (CNF_PATH_LAYERED), or thread-per-sample (CNF_PATH_SIMT) when a layer is wider than the product kernels cover.
+ * 3 is reserved (an internal form of tanh).
+ *   SIGMOID  1 / (1 + exp(-a))                                  NNlib.sigmoid, sigmoid_fast
+ *   SWISH    a sigmoid(a)                                       NNlib.swish (SiLU)
+ *   ELU      a for a >= 0, exp(a) - 1 below                     NNlib.elu, alpha = 1
+ *   GELU     a/2 (1 + tanh(sqrt(2/pi) (a + 0.044715 a^3)))      NNlib.gelu (tanh form) */
+enum {
+    CNF_ACT_IDENTITY = 0, CNF_ACT_TANH = 1, CNF_ACT_SOFTPLUS = 2,
+    CNF_ACT_SIGMOID = 4, CNF_ACT_SWISH = 5, CNF_ACT_ELU = 6, CNF_ACT_GELU = 7
+};
 
 /* trace estimator = ComputeMode x Mode of the reference:
  *   HUTCH_VJP  LuxVecJacMatrixMode / DIVecJacMatrixMode + TrainMode   (src/core/utils.jl:150-159)

@@ -4,7 +4,13 @@ act_id(::typeof(identity)) = Int32(0)
 act_id(::typeof(tanh)) = Int32(1)
 act_id(::typeof(NNlib.tanh_fast)) = Int32(1)         # Lux swaps tanh -> tanh_fast on CPU arrays; same function to 3e-7
 act_id(::typeof(NNlib.softplus)) = Int32(2)
-act_id(f::Any) = error("HIPMatrixMode: no kernel for activation $f (supported: identity, tanh, softplus)")
+act_id(::typeof(NNlib.sigmoid)) = Int32(4)           # also NNlib.σ (the same function)
+act_id(::typeof(NNlib.sigmoid_fast)) = Int32(4)      # Lux swaps sigmoid -> sigmoid_fast as it swaps tanh -> tanh_fast
+act_id(::typeof(NNlib.swish)) = Int32(5)
+act_id(::typeof(NNlib.elu)) = Int32(6)               # alpha = 1, elu's default
+act_id(::typeof(NNlib.gelu)) = Int32(7)              # tanh form
+act_id(f::Any) = error("HIPMatrixMode: no kernel for activation $f " *
+                       "(supported: identity, tanh, softplus, sigmoid, swish, elu, gelu)")
 
 "The `Lux.Dense` layers of `icnf.nn` (a `Lux.Chain` of `Dense`, src/core/icnf.jl:67-71), in order."
 function dense_layers(nn::LuxCore.AbstractLuxLayer)
