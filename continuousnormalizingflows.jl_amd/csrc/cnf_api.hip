@@ -62,11 +62,11 @@ bool build_pack_map(PackMap& m, size_t nparams, size_t npacked,
         if (std::memcmp(&want, &p3[j], sizeof(float)) != 0) return false;
     }
     if (m.n != npacked) {
-        if (m.idx) (void)hipFree(m.idx);
-        if (m.scale) (void)hipFree(m.scale);
-        m.idx = nullptr; m.scale = nullptr; m.n = 0;
-        if (hipMalloc((void**)&m.idx, npacked * sizeof(int)) != hipSuccess) return false;
-        if (hipMalloc((void**)&m.scale, npacked * sizeof(float)) != hipSuccess) return false;
+        m.idx.release();
+        m.scale.release();
+        m.n = 0;
+        if (m.idx.reserve(npacked) != hipSuccess) return false;
+        if (m.scale.reserve(npacked) != hipSuccess) return false;
         m.n = npacked;
     }
     if (hipMemcpy(m.idx, idx.data(), npacked * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return false;
@@ -75,10 +75,32 @@ bool build_pack_map(PackMap& m, size_t nparams, size_t npacked,
     return true;
 }
 
-void free_pack_map(PackMap& m) {
-    if (m.idx) (void)hipFree(m.idx);
-    if (m.scale) (void)hipFree(m.scale);
-    m = PackMap{};
+// image[j] = src[idx[j]] * scale[j] on `st`
+int gather(const PackMap& m, const float* src, float* image, hipStream_t st) {
+    hipLaunchKernelGGL(gather_pack_kernel, dim3((unsigned)((m.n + 255) / 256)), dim3(256), 0, st, src, m.idx.data(), m.scale.data(),
+                       image, m.n);
+    HIP_TRY(hipGetLastError());
+    return CNF_OK;
+}
+
+// An auxiliary gradient image of `bytes` bytes, gathered from the Lux-layout device copy: its map is rebuilt when the layout
+// changed; an image that turns out not to be a gather is dropped (the gradient routes test it for null)
+int gather_or_drop(cnf_handle* h, PackMap& map, DevBuf<float>& image, size_t bytes, size_t n, bool same_layout,
+                   const std::function<void(const float*, float*)>& pack, hipStream_t st) {
+    HIP_TRY(image.reserve(bytes / sizeof(float)));
+    if (!map.valid || !same_layout) build_pack_map(map, n, bytes / sizeof(float), pack);
+    if (!map.valid) {
+        image.release();
+        return CNF_OK;
+    }
+    return gather(map, h->par.P_dev, image, st);
+}
+
+// the Lux-layout device copy holds exactly n floats: a changed parameter count replaces it
+int ensure_p_dev(cnf_handle* h, size_t n) {
+    if (h->par.P_dev && h->par.n != n) h->par.P_dev.release();
+    HIP_TRY(h->par.P_dev.reserve(n));
+    return CNF_OK;
 }
 
 }  // namespace
@@ -86,21 +108,17 @@ void free_pack_map(PackMap& m) {
 
 static int ensure_ws(cnf_handle* h, int64_t B) {
     if (B <= h->simt.ws_B) return CNF_OK;
-    if (h->simt.ws) HIP_TRY(hipFree(h->simt.ws));
-    h->simt.ws = nullptr;
     h->simt.ws_B = 0;
     const int64_t Bp = (B + 255) / 256 * 256;
-    HIP_TRY(hipMalloc((void**)&h->simt.ws, simt_ws_rows(h->net) * (size_t)Bp * sizeof(float)));
+    HIP_TRY(h->simt.ws.reserve(simt_ws_rows(h->net) * (size_t)Bp));
     h->simt.ws_B = Bp;
     return CNF_OK;
 }
 
 static int ensure_kbuf(cnf_handle* h, int64_t B) {
     if (B <= h->simt.kbuf_B) return CNF_OK;
-    if (h->simt.kbuf) HIP_TRY(hipFree(h->simt.kbuf));
-    h->simt.kbuf = nullptr;
     h->simt.kbuf_B = 0;
-    HIP_TRY(hipMalloc((void**)&h->simt.kbuf, 7 * (size_t)h->S * (size_t)B * sizeof(float)));
+    HIP_TRY(h->simt.kbuf.reserve(7 * (size_t)h->S * (size_t)B));
     h->simt.kbuf_B = B;
     return CNF_OK;
 }
@@ -216,35 +234,10 @@ int cnf_destroy(cnf_handle* h) {
     if (!h) return CNF_OK;
     if (h->grad_twin) { cnf_destroy(h->grad_twin); h->grad_twin = nullptr; }
     DeviceGuard g(h->cfg.device_id);
-    if (h->par.P_dev) (void)hipFree(h->par.P_dev);
-    if (h->par.packed_dev) (void)hipFree(h->par.packed_dev);
-    if (h->simt.ws) (void)hipFree(h->simt.ws);
-    if (h->simt.kbuf) (void)hipFree(h->simt.kbuf);
-    if (h->loss_partial) (void)hipFree(h->loss_partial);
-    if (h->grad.packed) (void)hipFree(h->grad.packed);
-    if (h->grad.ws) (void)hipFree(h->grad.ws);
-    if (h->par.stage) (void)hipFree(h->par.stage);
-    if (h->emb.buf) (void)hipFree(h->emb.buf);
-    if (h->emb.err_partial) (void)hipFree(h->emb.err_partial);
-    if (h->vc.buf) (void)hipFree(h->vc.buf);
-    if (h->grad.tgrid_dev) (void)hipFree(h->grad.tgrid_dev);
-    if (h->grad.probe_ws) (void)hipFree(h->grad.probe_ws);
-    if (h->adp.buf) (void)hipFree(h->adp.buf);
-    if (h->adp.dc_buf) (void)hipFree(h->adp.dc_buf);
-    if (h->adp.host_rec) (void)hipHostFree(h->adp.host_rec);
-    if (h->vc.partial) (void)hipFree(h->vc.partial);
-    if (h->vc.host_res) (void)hipHostFree(h->vc.host_res);
     layered_grad_destroy(h->grad.layered);
-    free_pack_map(h->par.map_fwd);
-    free_pack_map(h->grad.map);
-    free_pack_map(h->grad.map_slab);
-    if (h->grad.slab_packed) (void)hipFree(h->grad.slab_packed);
-    if (h->grad.slab_ws) (void)hipFree(h->grad.slab_ws);
-    free_pack_map(h->grad.map_cg);
-    if (h->grad.cg_packed) (void)hipFree(h->grad.cg_packed);
     if (h->grad.plan_cg) mfma_plan_destroy(h->grad.plan_cg);
     if (h->plan) mfma_plan_destroy(h->plan);
-    delete h;
+    delete h;   // the buffers free themselves, with the handle's device current
     return CNF_OK;
 }
 
@@ -299,8 +292,8 @@ int cnf_set_params(cnf_handle* h, const float* p, size_t n, const size_t* w_off,
         h->par.b_off.assign(b_off, b_off + c.n_layers);
         h->par.maps_built = false;
     }
-    if (mfma && !h->par.packed_dev) HIP_TRY(hipMalloc((void**)&h->par.packed_dev, mfma_packed_bytes(h->plan)));
-    if (want_grad && !h->grad.packed) HIP_TRY(hipMalloc((void**)&h->grad.packed, grad_packed_bytes(gc)));
+    if (mfma) HIP_TRY(h->par.packed_dev.reserve(mfma_packed_bytes(h->plan) / sizeof(float)));
+    if (want_grad) HIP_TRY(h->grad.packed.reserve(grad_packed_bytes(gc) / sizeof(float)));
     if (mfma && !h->par.maps_built) {
         // one-time (per layout): derive and verify the gather maps from the host packers
         size_t qo = 0, ql = 0;
@@ -318,32 +311,17 @@ int cnf_set_params(cnf_handle* h, const float* p, size_t n, const size_t* w_off,
         // device path: (host p: one H2D copy into the staging buffer, then) gather kernels on `stream`
         const float* src = p;
         if (!p_is_device) {
-            if (h->par.stage_n < n) {
-                if (h->par.stage) HIP_TRY(hipFree(h->par.stage));
-                h->par.stage = nullptr; h->par.stage_n = 0;
-                HIP_TRY(hipMalloc((void**)&h->par.stage, n * sizeof(float)));
-                h->par.stage_n = n;
-            }
+            HIP_TRY(h->par.stage.reserve(n));
             HIP_TRY(hipMemcpyAsync(h->par.stage, p, n * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));   // the caller may reuse its host buffer on return
             src = h->par.stage;
         }
         // Lux-layout device copy (the layer-wise gradient reads the plain parameters)
-        if (h->par.P_dev && h->par.n != n) {
-            HIP_TRY(hipFree(h->par.P_dev));
-            h->par.P_dev = nullptr;
-        }
-        if (!h->par.P_dev) HIP_TRY(hipMalloc((void**)&h->par.P_dev, n * sizeof(float)));
+        if (int rc = ensure_p_dev(h, n)) return rc;
         HIP_TRY(hipMemcpyAsync(h->par.P_dev, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-        const PackMap* maps[2] = {&h->par.map_fwd, want_grad ? &h->grad.map : nullptr};
-        float* outs[2] = {h->par.packed_dev, h->grad.packed};
-        for (int i = 0; i < 2; ++i) {
-            if (!maps[i]) continue;
-            const size_t np = maps[i]->n;
-            hipLaunchKernelGGL(gather_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, src,
-                               maps[i]->idx, maps[i]->scale, outs[i], np);
-            HIP_TRY(hipGetLastError());
-        }
+        if (int rc = gather(h->par.map_fwd, src, h->par.packed_dev, st)) return rc;
+        if (want_grad)
+            if (int rc = gather(h->grad.map, src, h->grad.packed, st)) return rc;
         size_t qo = 0, ql = 0;
         if (mfma_plan_q_region(h->plan, &qo, &ql)) HIP_TRY(mfma_pack_q_device(h->plan, src, w_off, h->par.packed_dev, st));
     } else {
@@ -356,11 +334,7 @@ int cnf_set_params(cnf_handle* h, const float* p, size_t n, const size_t* w_off,
             std::memcpy(host.data(), p, n * sizeof(float));
         }
         if (mfma) {
-            if (h->par.P_dev && h->par.n != n) {
-                HIP_TRY(hipFree(h->par.P_dev));
-                h->par.P_dev = nullptr;
-            }
-            if (!h->par.P_dev) HIP_TRY(hipMalloc((void**)&h->par.P_dev, n * sizeof(float)));
+            if (int rc = ensure_p_dev(h, n)) return rc;
             HIP_TRY(hipMemcpyAsync(h->par.P_dev, host.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
             const size_t bytes = mfma_packed_bytes(h->plan);
             std::vector<float> packed(bytes / sizeof(float), 0.f);
@@ -375,11 +349,7 @@ int cnf_set_params(cnf_handle* h, const float* p, size_t n, const size_t* w_off,
                 HIP_TRY(hipStreamSynchronize(st));
             }
         } else {
-            if (h->par.P_dev && h->par.n != n) {
-                HIP_TRY(hipFree(h->par.P_dev));
-                h->par.P_dev = nullptr;
-            }
-            if (!h->par.P_dev) HIP_TRY(hipMalloc((void**)&h->par.P_dev, n * sizeof(float)));
+            if (int rc = ensure_p_dev(h, n)) return rc;
             HIP_TRY(hipMemcpyAsync(h->par.P_dev, host.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
             for (int l = 0; l < c.n_layers; ++l) {
@@ -390,20 +360,9 @@ int cnf_set_params(cnf_handle* h, const float* p, size_t n, const size_t* w_off,
     }
     // image of the slab-accumulator gradient kernel: a gather from the Lux-layout device copy kept above
     if (grad_slab_supported(c) && !(mfma && want_grad)) {
-        const size_t sb = grad_slab_packed_bytes(c);
-        if (!h->grad.slab_packed) HIP_TRY(hipMalloc((void**)&h->grad.slab_packed, sb));
-        if (!h->grad.map_slab.valid || !same_layout)
-            build_pack_map(h->grad.map_slab, n, sb / sizeof(float),
-                           [&](const float* src, float* dst) { grad_slab_pack(c, src, w_off, b_off, dst); });
-        if (h->grad.map_slab.valid) {
-            const size_t np = h->grad.map_slab.n;
-            hipLaunchKernelGGL(gather_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, h->par.P_dev,
-                               h->grad.map_slab.idx, h->grad.map_slab.scale, h->grad.slab_packed, np);
-            HIP_TRY(hipGetLastError());
-        } else {
-            HIP_TRY(hipFree(h->grad.slab_packed));
-            h->grad.slab_packed = nullptr;
-        }
+        const int rc = gather_or_drop(h, h->grad.map_slab, h->grad.slab_packed, grad_slab_packed_bytes(c), n, same_layout,
+                                      [&](const float* src, float* dst) { grad_slab_pack(c, src, w_off, b_off, dst); }, st);
+        if (rc) return rc;
     }
     // image of the auxiliary cooperative plan (see cnf_handle::plan_cg): two-layer slab shapes of 5 - 8 hidden tiles, one-probe VJP, no conditions
     if (grad_slab_supported(c) && !(mfma && want_grad) && c.mode == CNF_MODE_HUTCH_VJP && c.nprobes == 1 && c.ncond == 0 &&
@@ -413,20 +372,9 @@ int cnf_set_params(cnf_handle* h, const float* p, size_t n, const size_t* w_off,
             if (tuning().coop_grad_mid != 0) h->grad.plan_cg = mfma_plan_create(c, true);
         }
         if (h->grad.plan_cg) {
-            const size_t cb = mfma_packed_bytes(h->grad.plan_cg);
-            if (!h->grad.cg_packed) HIP_TRY(hipMalloc((void**)&h->grad.cg_packed, cb));
-            if (!h->grad.map_cg.valid || !same_layout)
-                build_pack_map(h->grad.map_cg, n, cb / sizeof(float),
-                               [&](const float* src, float* dst) { mfma_pack(h->grad.plan_cg, src, w_off, b_off, dst); });
-            if (h->grad.map_cg.valid) {
-                const size_t np = h->grad.map_cg.n;
-                hipLaunchKernelGGL(gather_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, h->par.P_dev,
-                                   h->grad.map_cg.idx, h->grad.map_cg.scale, h->grad.cg_packed, np);
-                HIP_TRY(hipGetLastError());
-            } else {
-                HIP_TRY(hipFree(h->grad.cg_packed));
-                h->grad.cg_packed = nullptr;
-            }
+            const int rc = gather_or_drop(h, h->grad.map_cg, h->grad.cg_packed, mfma_packed_bytes(h->grad.plan_cg), n, same_layout,
+                                          [&](const float* src, float* dst) { mfma_pack(h->grad.plan_cg, src, w_off, b_off, dst); }, st);
+            if (rc) return rc;
         }
     }
     h->par.n = n;
@@ -550,7 +498,7 @@ int cnf_inference_fixed(cnf_handle* h, int alg, int nsteps, float t0, float t1, 
     if (!x || !logp) return fail(CNF_ERR_INVALID, "cnf_inference_fixed: null x/logp");
     DeviceGuard g(h->cfg.device_id);
     hipStream_t st = (hipStream_t)stream;
-    const int reg_aug = (h->cfg.reg_aug && h->cfg.naug > 0 && h->cfg.mode != CNF_MODE_EXACT) ? 1 : 0;
+    const int reg_aug = api_reg_aug(h);
     if (h->path == CNF_PATH_MFMA) {
         SolveArgs a{};
         a.x = x; a.eps = eps; a.ys = ys; a.B = B; a.nsteps = nsteps; a.alg = alg;
@@ -669,9 +617,8 @@ int cnf::api_integrate_grid(cnf_handle* h, int alg, int nsteps, const float* tgr
                             int64_t B, hipStream_t st) {
     const size_t n = (size_t)h->S * (size_t)B;
     if (B > h->emb.B) {
-        if (h->emb.buf) HIP_TRY(hipFree(h->emb.buf));
-        h->emb.buf = nullptr; h->emb.B = 0;
-        HIP_TRY(hipMalloc((void**)&h->emb.buf, 8 * n * sizeof(float)));
+        h->emb.B = 0;
+        HIP_TRY(h->emb.buf.reserve(8 * n));
         h->emb.B = B;
     }
     const size_t slot = (size_t)h->S * (size_t)h->emb.B;
@@ -711,7 +658,7 @@ int cnf_epilogue(cnf_handle* h, const float* u, int64_t B, float* logp, float* r
     if (B == 0) return CNF_OK;
     if (!u || !logp) return fail(CNF_ERR_INVALID, "cnf_epilogue: null u/logp");
     DeviceGuard g(h->cfg.device_id);
-    const int reg_aug = (h->cfg.reg_aug && h->cfg.naug > 0 && h->cfg.mode != CNF_MODE_EXACT) ? 1 : 0;
+    const int reg_aug = api_reg_aug(h);
     HIP_TRY(epilogue(u, h->cfg.nvars, h->D, reg_aug, B, logp, regs, (hipStream_t)stream));
     return CNF_OK;
 }
@@ -721,7 +668,7 @@ int cnf_loss_sums(cnf_handle* h, const float* logp, const float* regs, int64_t B
     if (!h || !logp || !sums4) return fail(CNF_ERR_INVALID, "cnf_loss_sums: null argument");
     if (B < 0) return fail(CNF_ERR_INVALID, "cnf_loss_sums: negative batch");
     DeviceGuard g(h->cfg.device_id);
-    if (!h->loss_partial) HIP_TRY(hipMalloc((void**)&h->loss_partial, 256 * 4 * sizeof(float)));
+    HIP_TRY(api_loss_partial(h));
     HIP_TRY(loss_sums(logp, regs, B, h->loss_partial, sums4, (hipStream_t)stream));
     return CNF_OK;
 }
@@ -731,7 +678,7 @@ int cnf_loss_mean(cnf_handle* h, const float* logp, const float* regs, int64_t B
     if (!h || !logp || !lambdas || !loss) return fail(CNF_ERR_INVALID, "cnf_loss_mean: null argument");
     if (B < 1) return fail(CNF_ERR_INVALID, "cnf_loss_mean: the mean of an empty batch is undefined (use cnf_loss_sums on shards)");
     DeviceGuard g(h->cfg.device_id);
-    if (!h->loss_partial) HIP_TRY(hipMalloc((void**)&h->loss_partial, 256 * 4 * sizeof(float)));
+    HIP_TRY(api_loss_partial(h));
     HIP_TRY(loss_mean(logp, regs, B, h->loss_partial, sums4, loss, lambdas, (hipStream_t)stream));
     return CNF_OK;
 }

@@ -42,13 +42,12 @@ static int step_embedded_impl(cnf_handle* h, int alg, int flags, float t, float 
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)h->S * (size_t)B;
     if (B > h->emb.B) {
-        if (h->emb.buf) HIP_TRY(hipFree(h->emb.buf));
-        h->emb.buf = nullptr; h->emb.B = 0;
-        HIP_TRY(hipMalloc((void**)&h->emb.buf, 8 * n * sizeof(float)));
+        h->emb.B = 0;
+        HIP_TRY(h->emb.buf.reserve(8 * n));
         h->emb.B = B;
         flags = 0;   // the cached stages went with the old buffer
     }
-    if (!h->emb.err_partial) HIP_TRY(hipMalloc((void**)&h->emb.err_partial, kErrBlocks * sizeof(double)));
+    HIP_TRY(h->emb.err_partial.reserve(kErrBlocks));
     const size_t slot = (size_t)h->S * (size_t)h->emb.B;
     float* stage = h->emb.buf + 7 * slot;
     if (flags & CNF_STEP_FSAL) { const int tmp = h->emb.k[0]; h->emb.k[0] = h->emb.k[6]; h->emb.k[6] = tmp; }
@@ -106,6 +105,10 @@ extern "C" {
 
 // ---- variable-step variable-order Adams PECE: the reference's default alg = VCABM() ----
 
+// partial sums of the multistep solve's reductions + the result slots of cnf_solve_vcabm; pinned result slots of the host-driven loops
+static inline hipError_t vc_partial(cnf_handle* h) { return h->vc.partial.reserve(vcabm_partial_doubles() + 8); }
+static inline hipError_t vc_host_res(cnf_handle* h) { return h->vc.host_res.reserve(8); }
+
 static inline float* vc_vec(cnf_handle* h, int i) { return h->vc.buf + (size_t)i * (size_t)h->S * (size_t)h->vc.B; }
 static inline float* vc_diffs(cnf_handle* h, int half) { return vc_vec(h, 6 + half * kVcSlots); }
 
@@ -123,13 +126,12 @@ int cnf_vcabm_begin(cnf_handle* h, float t0, const float* u0, const float* eps, 
     DeviceGuard g(h->cfg.device_id);
     hipStream_t st = (hipStream_t)stream;
     if (B > h->vc.cap) {   // grown on demand only: alternating batch sizes (a shorter last mini-batch) reuse the allocation
-        if (h->vc.buf) HIP_TRY(hipFree(h->vc.buf));
-        h->vc.buf = nullptr; h->vc.cap = 0; h->vc.B = -1;
-        HIP_TRY(hipMalloc((void**)&h->vc.buf, (6 + 2 * kVcSlots) * (size_t)h->S * (size_t)B * sizeof(float)));
+        h->vc.cap = 0; h->vc.B = -1;
+        HIP_TRY(h->vc.buf.reserve((6 + 2 * kVcSlots) * (size_t)h->S * (size_t)B));
         h->vc.cap = B;
     }
     h->vc.B = B;   // the vectors of this solve are packed at stride S x B inside the allocation
-    if (!h->vc.partial) HIP_TRY(hipMalloc((void**)&h->vc.partial, (vcabm_partial_doubles() + 8) * sizeof(double)));   // + result slots of cnf_solve_vcabm
+    HIP_TRY(vc_partial(h));
     h->vc.iu = 0; h->vc.iun = 2; h->vc.ifn0 = 3; h->vc.ifn1 = 5; h->vc.cur = 0;
     h->vc.nhist = 0; h->vc.k = 0; h->vc.avail = 0; h->vc.m = 0; h->vc.t = t0; h->vc.dt = 0.0;
     for (double& d : h->vc.hist) d = 0.0;
@@ -260,6 +262,49 @@ int cnf_vcabm_state(cnf_handle* h, int64_t B, float* u_out, double* t_out, void*
     return CNF_OK;
 }
 
+// ---- what the one-launch adaptive solves (cnf_solve_vcabm, api_solve_tsit5) share ----
+
+// scratch for B columns and `dts_cap` recorded steps, the pinned record of status words and first steps, the argument block
+static int one_launch_setup(cnf_handle* h, float t0, float t1, const float* u0, const float* eps, const float* ys, int64_t B,
+                            int maxiters, float* u1, SolveArgs* a, int* dts_cap) {
+    h->adp.last_controller = 1;
+    *dts_cap = maxiters < (1 << 20) ? maxiters : (1 << 20);
+    const size_t need = mfma_adaptive_scratch_bytes(B, *dts_cap);
+    if (need > h->adp.dc_buf.capacity()) h->adp.dc_epoch = 0;   // a new allocation starts a new epoch
+    HIP_TRY(h->adp.dc_buf.reserve(need));
+    *a = SolveArgs{};
+    a->u0 = u0; a->eps = eps; a->ys = ys; a->B = B; a->nsteps = 1; a->alg = CNF_ALG_TSIT5; a->t0 = t0; a->t1 = t1;
+    a->u_out = u1; a->nvars = h->cfg.nvars; a->reg_aug = 0;
+    HIP_TRY(h->adp.host_rec.reserve(8 + 2 * kHostRec));
+    return CNF_OK;
+}
+
+// the status words of the pinned record: [3] how the solve ended, [5] a grid-wide sum that timed out
+static int one_launch_status(const int* hs, const char* who) {
+    const std::string w(who);
+    if (hs[3] == 1) return fail(CNF_ERR_INVALID, w + ": non-finite error estimate (unstable dynamics)");
+    if (hs[3] == 2) return fail(CNF_ERR_INVALID, w + ": maxiters reached");
+    if (hs[3] == 3) return fail(CNF_ERR_INVALID, w + ": non-finite state or dynamics at t0 (no initial step)");
+    if (hs[3] == 4 || hs[5] != 0) return fail(CNF_ERR_HIP, w + ": the grid-wide sum of the one-launch solve timed out (workgroups not all resident); CNF_DEVICE_CONTROLLER=0 selects the host loop");
+    return CNF_OK;
+}
+
+// the first `na` accepted steps (and their orders): read from the pinned record when it holds them all, else copied from the device
+static int one_launch_steps(const int* hs, int na, const float* dts_dev, const int* orders_dev, float* dts_out, int32_t* orders_out,
+                            hipStream_t st) {
+    if (na <= kHostRec) {
+        for (int i = 0; i < na; ++i) {
+            if (dts_out) memcpy(dts_out + i, hs + 8 + 2 * i, sizeof(float));
+            if (orders_out) orders_out[i] = hs[9 + 2 * i];
+        }
+        return CNF_OK;
+    }
+    if (dts_out) HIP_TRY(hipMemcpyAsync(dts_out, dts_dev, (size_t)na * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (orders_out) HIP_TRY(hipMemcpyAsync(orders_out, orders_dev, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (dts_out || orders_out) HIP_TRY(hipStreamSynchronize(st));
+    return CNF_OK;
+}
+
 // The whole default solve in one call: cnf_vcabm_begin / _attempt / _accept driven by the step-size and order policy of
 // solvers._vcabm_integrate (the host side of the reference's solver), restated here so that a single-process caller pays one
 // library call per solve instead of two per step.  Synchronises `stream` (the policy reads the error sums).
@@ -275,24 +320,15 @@ int cnf_solve_vcabm(cnf_handle* h, float t0, float t1, const float* u0, const fl
     if (maxiters < 1) return fail(CNF_ERR_INVALID, "cnf_solve_vcabm: maxiters >= 1 required");
     if (B > 0 && t1 != t0 && h->path == CNF_PATH_MFMA && h->plan && B <= mfma_vcabm_capacity(h->plan)) {
         // the batch fits the chip's wave slots: passes, error norms and the step / order policy in one launch
-        h->adp.last_controller = 1;
         DeviceGuard g(h->cfg.device_id);
         hipStream_t st = (hipStream_t)stream;
-        const int dts_cap = maxiters < (1 << 20) ? maxiters : (1 << 20);
-        const size_t need = mfma_adaptive_scratch_bytes(B, dts_cap);
-        if (need > h->adp.dc_bytes) {
-            if (h->adp.dc_buf) HIP_TRY(hipFree(h->adp.dc_buf));
-            h->adp.dc_buf = nullptr; h->adp.dc_bytes = 0; h->adp.dc_epoch = 0;
-            HIP_TRY(hipMalloc(&h->adp.dc_buf, need));
-            h->adp.dc_bytes = need;
-        }
-        SolveArgs a{};
-        a.u0 = u0; a.eps = eps; a.ys = ys; a.B = B; a.nsteps = 1; a.alg = CNF_ALG_TSIT5; a.t0 = t0; a.t1 = t1;
-        a.u_out = u1; a.nvars = h->cfg.nvars; a.reg_aug = 0;
+        SolveArgs a;
+        int dts_cap = 0;
+        rc = one_launch_setup(h, t0, t1, u0, eps, ys, B, maxiters, u1, &a, &dts_cap);
+        if (rc) return rc;
         int *stats_dev = nullptr, *orders_dev = nullptr;
         float* dts_dev = nullptr;
-        if (!h->adp.host_rec) HIP_TRY(hipHostMalloc((void**)&h->adp.host_rec, (8 + 2 * kHostRec) * sizeof(int), hipHostMallocDefault));
-        const hipError_t le = mfma_solve_vcabm(h->plan, h->par.packed_dev, a, abstol, reltol, dt_init, maxiters, h->adp.dc_buf, &h->adp.dc_epoch, dts_cap,
+        const hipError_t le = mfma_solve_vcabm(h->plan, h->par.packed_dev, a, abstol, reltol, dt_init, maxiters, h->adp.dc_buf.data(), &h->adp.dc_epoch, dts_cap,
                                                &stats_dev, &dts_dev, &orders_dev, h->adp.host_rec, st);
         if (le != hipSuccess) {
             (void)hipGetLastError();
@@ -302,21 +338,10 @@ int cnf_solve_vcabm(cnf_handle* h, float t0, float t1, const float* u0, const fl
         HIP_TRY(hipStreamSynchronize(st));
         const int* hs = h->adp.host_rec;
         if (stats) { stats->naccept = hs[0]; stats->nreject = hs[1]; stats->nf = hs[2]; stats->max_order = hs[4]; }
-        if (hs[3] == 1) return fail(CNF_ERR_INVALID, "cnf_solve_vcabm: non-finite error estimate (unstable dynamics)");
-        if (hs[3] == 2) return fail(CNF_ERR_INVALID, "cnf_solve_vcabm: maxiters reached");
-        if (hs[3] == 3) return fail(CNF_ERR_INVALID, "cnf_solve_vcabm: non-finite state or dynamics at t0 (no initial step)");
-        if (hs[3] == 4 || hs[5] != 0) return fail(CNF_ERR_HIP, "cnf_solve_vcabm: the grid-wide sum of the one-launch solve timed out (workgroups not all resident); CNF_DEVICE_CONTROLLER=0 selects the host loop");
-        const int na = std::min(std::min(hs[0], dts_cap), (int)record_cap);
-        if (na <= kHostRec) {
-            for (int i = 0; i < na; ++i) {
-                if (dts_out) memcpy(dts_out + i, hs + 8 + 2 * i, sizeof(float));
-                if (orders_out) orders_out[i] = hs[9 + 2 * i];
-            }
-        } else {
-            if (dts_out) HIP_TRY(hipMemcpyAsync(dts_out, dts_dev, (size_t)na * sizeof(float), hipMemcpyDeviceToHost, st));
-            if (orders_out) HIP_TRY(hipMemcpyAsync(orders_out, orders_dev, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            if (dts_out || orders_out) HIP_TRY(hipStreamSynchronize(st));
-        }
+        rc = one_launch_status(hs, "cnf_solve_vcabm");
+        if (rc) return rc;
+        rc = one_launch_steps(hs, std::min(std::min(hs[0], dts_cap), (int)record_cap), dts_dev, orders_dev, dts_out, orders_out, st);
+        if (rc) return rc;
         h->vc.B = -1;   // the step-wise entry points have no state from this solve
         return CNF_OK;
     }
@@ -333,7 +358,7 @@ int cnf_solve_vcabm(cnf_handle* h, float t0, float t1, const float* u0, const fl
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)h->S * (size_t)B;
     const double ntot = (double)n;
-    if (!h->vc.host_res) HIP_TRY(hipHostMalloc((void**)&h->vc.host_res, 8 * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(vc_host_res(h));
     double* res = h->vc.host_res;   // result slots in pinned host memory: the reduction kernels write them, the loop synchronises and reads
     double host[4];
     auto fetch = [&](int cnt) -> int {
@@ -423,9 +448,8 @@ int cnf_solve_vcabm(cnf_handle* h, float t0, float t1, const float* u0, const fl
 extern "C++" {
 int cnf::api_ensure_adaptive_buf(cnf_handle* h, int64_t B) {
     if (B <= h->adp.B) return CNF_OK;
-    if (h->adp.buf) HIP_TRY(hipFree(h->adp.buf));
-    h->adp.buf = nullptr; h->adp.B = 0;
-    HIP_TRY(hipMalloc((void**)&h->adp.buf, 6 * (size_t)h->S * (size_t)B * sizeof(float)));   // 4 for the solve, 2 for cnf_loss_grad_adaptive
+    h->adp.B = 0;
+    HIP_TRY(h->adp.buf.reserve(6 * (size_t)h->S * (size_t)B));   // 4 for the solve, 2 for cnf_loss_grad_adaptive
     h->adp.B = B;
     return CNF_OK;
 }
@@ -454,23 +478,14 @@ int cnf::api_solve_tsit5(cnf_handle* h, float t0, float t1, const float* u0, con
     }
     if (h->path == CNF_PATH_MFMA && h->plan && B <= mfma_adaptive_capacity(h->plan)) {
         // the batch fits the chip's wave slots: the whole solve, step controller included, in one launch
-        h->adp.last_controller = 1;
-        const int dts_cap = maxiters < (1 << 20) ? maxiters : (1 << 20);
-        const size_t need = mfma_adaptive_scratch_bytes(B, dts_cap);
-        if (need > h->adp.dc_bytes) {
-            if (h->adp.dc_buf) HIP_TRY(hipFree(h->adp.dc_buf));
-            h->adp.dc_buf = nullptr; h->adp.dc_bytes = 0; h->adp.dc_epoch = 0;
-            HIP_TRY(hipMalloc(&h->adp.dc_buf, need));
-            h->adp.dc_bytes = need;
-        }
-        SolveArgs a{};
-        a.u0 = u0; a.eps = eps; a.ys = ys; a.B = B; a.nsteps = 1; a.alg = CNF_ALG_TSIT5; a.t0 = t0; a.t1 = t1;
-        a.u_out = u1; a.nvars = h->cfg.nvars; a.reg_aug = 0;
+        SolveArgs a;
+        int dts_cap = 0;
+        rc = one_launch_setup(h, t0, t1, u0, eps, ys, B, maxiters, u1, &a, &dts_cap);
+        if (rc) return rc;
         if (ck && ck->cap > 0) { a.ckpt = ck->ckpt; a.ckpt_k = ck->ckpt_k; }
         int* stats_dev = nullptr;
         float* dts_dev = nullptr;
-        if (!h->adp.host_rec) HIP_TRY(hipHostMalloc((void**)&h->adp.host_rec, (8 + 2 * kHostRec) * sizeof(int), hipHostMallocDefault));
-        const hipError_t le = mfma_solve_adaptive(h->plan, h->par.packed_dev, a, abstol, reltol, dt_init, maxiters, h->adp.dc_buf, &h->adp.dc_epoch, dts_cap, &stats_dev, &dts_dev,
+        const hipError_t le = mfma_solve_adaptive(h->plan, h->par.packed_dev, a, abstol, reltol, dt_init, maxiters, h->adp.dc_buf.data(), &h->adp.dc_epoch, dts_cap, &stats_dev, &dts_dev,
                                                   h->adp.host_rec, ck ? ck->cap : 0, st);
         if (le != hipSuccess) {
             (void)hipGetLastError();   // not sticky: nothing was launched
@@ -480,20 +495,14 @@ int cnf::api_solve_tsit5(cnf_handle* h, float t0, float t1, const float* u0, con
         HIP_TRY(hipStreamSynchronize(st));
         const int* host = h->adp.host_rec;
         if (stats) { stats->naccept = host[0]; stats->nreject = host[1]; stats->nf = host[2]; stats->max_order = 5; }
-        if (host[3] == 1) return fail(CNF_ERR_INVALID, "cnf_solve_tsit5: non-finite error estimate (unstable dynamics)");
-        if (host[3] == 2) return fail(CNF_ERR_INVALID, "cnf_solve_tsit5: maxiters reached");
-        if (host[3] == 3) return fail(CNF_ERR_INVALID, "cnf_solve_tsit5: non-finite state or dynamics at t0 (no initial step)");
-        if (host[3] == 4 || host[5] != 0) return fail(CNF_ERR_HIP, "cnf_solve_tsit5: the grid-wide sum of the one-launch solve timed out (workgroups not all resident); CNF_DEVICE_CONTROLLER=0 selects the host loop");
+        rc = one_launch_status(host, "cnf_solve_tsit5");
+        if (rc) return rc;
         if (ck) ck->ok = ck->cap > 0 && host[6] == 1;
         if (steps) {
             const int na = host[0] < dts_cap ? host[0] : dts_cap;
             std::vector<float> all((size_t)na);
-            if (na <= kHostRec) {
-                for (int i = 0; i < na; ++i) memcpy(&all[i], host + 8 + 2 * i, sizeof(float));
-            } else {
-                HIP_TRY(hipMemcpyAsync(all.data(), dts_dev, (size_t)na * sizeof(float), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-            }
+            rc = one_launch_steps(host, na, dts_dev, nullptr, all.data(), nullptr, st);
+            if (rc) return rc;
             for (int i = 0; i < na; ++i) steps->push_back((double)all[i]);
         }
         return CNF_OK;
@@ -501,11 +510,11 @@ int cnf::api_solve_tsit5(cnf_handle* h, float t0, float t1, const float* u0, con
     h->adp.last_controller = 0;
     rc = api_ensure_adaptive_buf(h, B);
     if (rc) return rc;
-    if (!h->vc.partial) HIP_TRY(hipMalloc((void**)&h->vc.partial, (vcabm_partial_doubles() + 8) * sizeof(double)));
+    HIP_TRY(vc_partial(h));
     const size_t slot = (size_t)h->S * (size_t)h->adp.B;
     float *ua = h->adp.buf, *ub = ua + slot, *f0 = ub + slot, *f1 = f0 + slot;
     HIP_TRY(hipMemcpyAsync(ua, u0, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (!h->vc.host_res) HIP_TRY(hipHostMalloc((void**)&h->vc.host_res, 8 * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(vc_host_res(h));
     double* res = h->vc.host_res;   // pinned host memory, as in cnf_solve_vcabm
     double host[2];
     auto fetch = [&](int cnt) -> int {
@@ -618,9 +627,8 @@ int cnf_loss_adaptive(cnf_handle* h, int alg, float t0, float t1, const float* x
     // u0 is spent: its slot (S >= 4 floats per column) takes the per-sample outputs the caller did not ask for
     float* logp = logp_out ? logp_out : u0;
     float* regs = regs_out ? regs_out : u0 + B;
-    const int reg_aug = (h->cfg.reg_aug && h->cfg.naug > 0 && h->cfg.mode != CNF_MODE_EXACT) ? 1 : 0;
-    HIP_TRY(epilogue(u1, h->cfg.nvars, h->D, reg_aug, B, logp, regs, st));
-    if (!h->loss_partial) HIP_TRY(hipMalloc((void**)&h->loss_partial, 256 * 4 * sizeof(float)));
+    HIP_TRY(epilogue(u1, h->cfg.nvars, h->D, api_reg_aug(h), B, logp, regs, st));
+    HIP_TRY(api_loss_partial(h));
     HIP_TRY(loss_mean(logp, regs, B, h->loss_partial, sums4, loss, lambdas, st));
     return CNF_OK;
 }

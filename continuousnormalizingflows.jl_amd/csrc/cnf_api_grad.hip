@@ -136,7 +136,7 @@ int cnf_grad_form_for(const cnf_handle* h, int64_t B, int alg, int nsteps, int o
 // Layout of the fused per-wave gradient's workspace (cnf_handle::grad.ws) for `steps` steps: z checkpoints (steps + 1 slots), stage
 // derivatives (steps x stages slots), logp + regs (4 B), the gradient slabs, the ping-pong states of a grid's step-by-step forward
 // pass, the unit probes of TestMode.
-struct FusedWs { size_t ckpt_z_floats, ckpt_k_floats, slab_floats, state_floats, unit_floats, need; };
+struct FusedWs { size_t ckpt_z_floats, ckpt_k_floats, slab_floats, state_floats, unit_floats, need_floats; };
 static FusedWs fused_ws(cnf_handle* h, int alg, int steps, int64_t B, bool on_grid) {
     FusedWs W{};
     const size_t ntiles = (size_t)((B + 15) / 16);
@@ -147,7 +147,21 @@ static FusedWs fused_ws(cnf_handle* h, int alg, int steps, int64_t B, bool on_gr
     W.slab_floats = grad_slab_floats(api_grad_cfg(h), h->num_cus);
     W.state_floats = on_grid ? 2 * (size_t)h->S * (size_t)B : 0;
     W.unit_floats = h->cfg.mode == CNF_MODE_EXACT ? (size_t)h->D * (size_t)h->D * (size_t)B : 0;
-    W.need = (W.ckpt_z_floats + W.ckpt_k_floats + 4 * (size_t)B + W.slab_floats + W.state_floats + W.unit_floats) * sizeof(float);
+    W.need_floats = W.ckpt_z_floats + W.ckpt_k_floats + 4 * (size_t)B + W.slab_floats + W.state_floats + W.unit_floats;
+    return W;
+}
+
+// Layout of the same workspace on the other routes: logp, regs and one augmented state ((S + 4) B floats) at its head; behind them,
+// where a forward solve hands its checkpoints to the slab-accumulator kernel, z checkpoints (steps + 1 slots) and stage derivatives
+// (steps x stages slots) in the layout of the forward instance, whose state rows `zr` gives (0: no checkpoints)
+struct SharedWs { size_t head, ckpt_k_off, need_floats; };   // the z checkpoints start at `head`
+static SharedWs shared_ws(const cnf_handle* h, int zr, int alg, int steps, int64_t B) {
+    SharedWs W{};
+    const int nstages = alg == CNF_ALG_RK4 ? 4 : 6;
+    const size_t zslot = (size_t)((B + 15) / 16) * 64 * (size_t)zr;
+    W.head = ((size_t)h->S + 4) * (size_t)B;
+    W.ckpt_k_off = W.head + (size_t)(steps + 1) * zslot;
+    W.need_floats = W.head + (size_t)((nstages + 1) * steps + 1) * zslot;
     return W;
 }
 
@@ -184,12 +198,7 @@ static int loss_grad_probe_loop(cnf_handle* h, cnf_handle* one, int K, const cha
     hipStream_t st = (hipStream_t)stream;
     const size_t D = (size_t)h->D, n = h->par.n, nx = grad_x ? (size_t)B * (size_t)h->cfg.nvars : 0;
     const size_t need = D * (size_t)B + n + nx + 4 + 16;
-    if (need > h->grad.probe_ws_floats) {
-        if (h->grad.probe_ws) HIP_TRY(hipFree(h->grad.probe_ws));
-        h->grad.probe_ws = nullptr; h->grad.probe_ws_floats = 0;
-        HIP_TRY(hipMalloc((void**)&h->grad.probe_ws, need * sizeof(float)));
-        h->grad.probe_ws_floats = need;
-    }
+    HIP_TRY(h->grad.probe_ws.reserve(need));
     float* eps_p = h->grad.probe_ws;
     float* grad_p = eps_p + (D * (size_t)B + 3) / 4 * 4;
     float* gx_p = grad_x ? grad_p + (n + 3) / 4 * 4 : nullptr;
@@ -244,13 +253,7 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
     const float* tgrid_dev = nullptr;
     if (tgrid) {   // the fused kernels read the step times from device memory (uniform loads, once per step)
         t0 = tgrid[0]; t1 = tgrid[nsteps];
-        if ((size_t)nsteps + 1 > h->grad.tgrid_cap) {
-            if (h->grad.tgrid_dev) HIP_TRY(hipFree(h->grad.tgrid_dev));
-            h->grad.tgrid_dev = nullptr; h->grad.tgrid_cap = 0;
-            const size_t cap = ((size_t)nsteps + 1 + 63) / 64 * 64;
-            HIP_TRY(hipMalloc((void**)&h->grad.tgrid_dev, cap * sizeof(float)));
-            h->grad.tgrid_cap = cap;
-        }
+        HIP_TRY(h->grad.tgrid_dev.reserve(((size_t)nsteps + 1 + 63) / 64 * 64));
         HIP_TRY(hipMemcpyAsync(h->grad.tgrid_dev, tgrid, ((size_t)nsteps + 1) * sizeof(float), hipMemcpyHostToDevice, st));
         tgrid_dev = h->grad.tgrid_dev;
     }
@@ -264,40 +267,30 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
         // forward instance's layout, kept behind the loss workspace - the kernel, which then runs no forward sweep of its own
         const bool slab_shared = route.slab && !tgrid && sums4 && tuning().adaptive_ckpt != 0 && h->path == CNF_PATH_MFMA && h->plan &&
                                  mfma_plan_is_per_wave(h->plan) && h->par.packed_dev;
-        const size_t sh_zslot = slab_shared ? (size_t)((B + 15) / 16) * 64 * (size_t)mfma_plan_zr(h->plan) : 0;
-        const int sh_stages = alg == CNF_ALG_RK4 ? 4 : 6;
-        const size_t sh_head = ((size_t)h->S + 4) * (size_t)B;
+        const SharedWs SW = shared_ws(h, slab_shared ? mfma_plan_zr(h->plan) : 0, alg, nsteps, B);
         const float *sh_ckpt = nullptr, *sh_ckpt_k = nullptr;
         if (sums4) {
-            const size_t need = (sh_head + (slab_shared ? (size_t)((sh_stages + 1) * nsteps + 1) * sh_zslot : 0)) * sizeof(float);
-            if (need > h->grad.ws_bytes) {
-                if (h->grad.ws) HIP_TRY(hipFree(h->grad.ws));
-                h->grad.ws = nullptr; h->grad.ws_bytes = 0;
-                HIP_TRY(hipMalloc((void**)&h->grad.ws, need));
-                h->grad.ws_bytes = need;
-            }
+            HIP_TRY(h->grad.ws.reserve(SW.need_floats));
             float* logp = h->grad.ws;
             float* regs = logp + B;
             if (loss_in_sweep) {
                 // the layer-wise reverse sweep accumulates the loss terms of the solve it differentiates (below)
             } else if (tgrid && pc && pc->u_final) {
                 // the adaptive solve that found the grid has the state at t1: its loss terms, no second solve over the grid
-                const int ra0 = (h->cfg.mode != CNF_MODE_EXACT && h->cfg.reg_aug && h->cfg.naug > 0) ? 1 : 0;
-                HIP_TRY(epilogue(pc->u_final, h->cfg.nvars, h->D, ra0, B, logp, regs, st));
+                HIP_TRY(epilogue(pc->u_final, h->cfg.nvars, h->D, api_reg_aug(h), B, logp, regs, st));
             } else if (tgrid) {   // the loss of the same discrete solve: augmented state advanced over the grid, then the epilogue
                 float* u = regs + 3 * (size_t)B;
-                const int ra0 = (h->cfg.mode != CNF_MODE_EXACT && h->cfg.reg_aug && h->cfg.naug > 0) ? 1 : 0;
                 HIP_TRY(assemble_u0(x, h->cfg.nvars, h->S, B, u, st));
                 rc = api_integrate_grid(h, alg, nsteps, tgrid, u, eps, ys, B, st);
                 if (rc) return rc;
-                HIP_TRY(epilogue(u, h->cfg.nvars, h->D, ra0, B, logp, regs, st));
+                HIP_TRY(epilogue(u, h->cfg.nvars, h->D, api_reg_aug(h), B, logp, regs, st));
             } else if (slab_shared) {
-                float* ck = h->grad.ws + sh_head;
-                float* ckk = ck + (size_t)(nsteps + 1) * sh_zslot;
+                float* ck = h->grad.ws + SW.head;
+                float* ckk = h->grad.ws + SW.ckpt_k_off;
                 SolveArgs a{};
                 a.x = x; a.eps = eps; a.ys = ys; a.B = B; a.nsteps = nsteps; a.alg = alg; a.t0 = t0; a.t1 = t1;
                 a.logp = logp; a.regs = regs; a.nvars = h->cfg.nvars;
-                a.reg_aug = (h->cfg.mode != CNF_MODE_EXACT && h->cfg.reg_aug && h->cfg.naug > 0) ? 1 : 0;
+                a.reg_aug = api_reg_aug(h);
                 a.ckpt = ck; a.ckpt_k = ckk;
                 HIP_TRY(mfma_solve(h->plan, h->par.packed_dev, a, st));
                 sh_ckpt = ck; sh_ckpt_k = ckk;
@@ -305,26 +298,16 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
                 rc = cnf_inference_fixed(h, alg, nsteps, t0, t1, x, eps, ys, B, logp, regs, nullptr, stream);
                 if (rc) return rc;
             }
-            if (!h->loss_partial) HIP_TRY(hipMalloc((void**)&h->loss_partial, 256 * 4 * sizeof(float)));
+            HIP_TRY(api_loss_partial(h));
             if (!loss_in_sweep) HIP_TRY(loss_sums(logp, regs, B, h->loss_partial, sums4, st));
         }
         const bool hutch = h->cfg.mode != CNF_MODE_EXACT;   // the exact-trace dynamics carry no regularisers (icnf.jl:297-339)
-        const int ra = (hutch && h->cfg.reg_aug && h->cfg.naug > 0) ? 1 : 0;
+        const int ra = api_reg_aug(h);
         const float lam[3] = {hutch && h->cfg.reg_z ? lambdas[0] : 0.f, hutch && h->cfg.reg_j ? lambdas[1] : 0.f, ra ? lambdas[2] : 0.f};
         if (route.slab) {
             // two-hidden-layer nets of 4..7 hidden tiles: tile-fused reverse sweep with slab accumulators (cnf_grad_slab.hip)
-            if (h->num_cus == 0) {
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, h->cfg.device_id));
-                h->num_cus = prop.multiProcessorCount;
-            }
-            const size_t need = grad_slab_ws_floats(h->cfg, alg, nsteps, B, h->num_cus);
-            if (need > h->grad.slab_ws_floats) {
-                if (h->grad.slab_ws) HIP_TRY(hipFree(h->grad.slab_ws));
-                h->grad.slab_ws = nullptr; h->grad.slab_ws_floats = 0;
-                HIP_TRY(hipMalloc((void**)&h->grad.slab_ws, need * sizeof(float)));
-                h->grad.slab_ws_floats = need;
-            }
+            HIP_TRY(api_num_cus(h));
+            HIP_TRY(h->grad.slab_ws.reserve(grad_slab_ws_floats(h->cfg, alg, nsteps, B, h->num_cus)));
             const bool pre = pc && pc->cap > 0 && pc->ckpt && pc->ckpt_k && tgrid;
             const float* pk = pre ? pc->ckpt : sh_ckpt;
             const float* pkk = pre ? pc->ckpt_k : sh_ckpt_k;
@@ -340,14 +323,14 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
             if (!cgi) return fail(CNF_ERR_NO_PARAMS, w + ": cnf_set_params has not been called");
             // wide hidden layers on the cooperative kernels: checkpointing forward solve (which also yields the loss terms),
             // one reverse-sweep launch per step, deferred weight-cotangent products (cnf_coop_grad.hip)
-            float* cg_logp = sums4 ? h->grad.ws : nullptr;
+            float* cg_logp = sums4 ? h->grad.ws.data() : nullptr;
             hipError_t e = coop_grad(&h->grad.layered, h->cfg, cgp, cgi, h->par.w_off.data(), h->par.b_off.data(), x, eps, ys, alg, nsteps,
                                      t0, t1, tgrid, tgrid_dev, B, lam, grad, grad_x, cg_logp, cg_logp ? cg_logp + B : nullptr, st, &msg);
             if (e != hipSuccess) return fail(CNF_ERR_HIP, w + ": " + msg);
             if (sums4) HIP_TRY(loss_sums(cg_logp, cg_logp + B, B, h->loss_partial, sums4, st));
             return CNF_OK;
         }
-        float* lg_logp = loss_in_sweep ? h->grad.ws : nullptr;
+        float* lg_logp = loss_in_sweep ? h->grad.ws.data() : nullptr;
         hipError_t e = layered_grad(&h->grad.layered, h->cfg, h->par.P_dev, h->par.w_off.data(), h->par.b_off.data(), x, eps, ys, alg, nsteps,
                                     t0, t1, tgrid, B, lam, grad, grad_x, st, &msg, lg_logp, lg_logp ? lg_logp + B : nullptr);
         if (e == hipErrorNotSupported) return fail(CNF_ERR_UNSUPPORTED, w + ": " + msg);
@@ -355,11 +338,7 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
         if (loss_in_sweep) HIP_TRY(loss_sums(lg_logp, lg_logp + B, B, h->loss_partial, sums4, st));
         return CNF_OK;
     }
-    if (h->num_cus == 0) {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, h->cfg.device_id));
-        h->num_cus = prop.multiProcessorCount;
-    }
+    HIP_TRY(api_num_cus(h));
     const long long ntiles = (B + 15) / 16;
     const int ckpt_zr = mfma_plan_zr(h->plan);
     const int nstages = alg == CNF_ALG_RK4 ? 4 : 6;
@@ -368,13 +347,8 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
     // (checkpoints an adaptive solve has written sit in arrays laid out for pc->cap steps, of which the first nsteps are filled)
     if (pc && pc->cap <= 0) pc = nullptr;   // (a final state without checkpoints serves the other implementations' loss terms only)
     const FusedWs W = fused_ws(h, alg, pc ? pc->cap : nsteps, B, tgrid != nullptr);
-    if (W.need > h->grad.ws_bytes) {
-        if (pc) return fail(CNF_ERR_INVALID, w + ": prepared checkpoints without their workspace");
-        if (h->grad.ws) HIP_TRY(hipFree(h->grad.ws));
-        h->grad.ws = nullptr; h->grad.ws_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&h->grad.ws, W.need));
-        h->grad.ws_bytes = W.need;
-    }
+    if (pc && W.need_floats > h->grad.ws.capacity()) return fail(CNF_ERR_INVALID, w + ": prepared checkpoints without their workspace");
+    HIP_TRY(h->grad.ws.reserve(W.need_floats));
     const size_t slab_floats = W.slab_floats, state_floats = W.state_floats, unit_floats = W.unit_floats;
     float* ckpt = h->grad.ws;
     float* ckpt_k = ckpt + W.ckpt_z_floats;
@@ -382,7 +356,7 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
     float* regs = logp + B;
     float* slab = regs + 3 * (size_t)B;
     (void)unit_floats;
-    const int reg_aug = (!exact && h->cfg.reg_aug && h->cfg.naug > 0) ? 1 : 0;
+    const int reg_aug = api_reg_aug(h);
     if (pc) {
         // the solve that found the grid has left z_n and the stage derivatives of its accepted steps in ckpt / ckpt_k: no forward
         // pass; the loss terms are those of its final state
@@ -410,7 +384,7 @@ static int loss_grad_impl(cnf_handle* h, const char* who, int alg, int nsteps, f
         }
     }
     if (sums4) {
-        if (!h->loss_partial) HIP_TRY(hipMalloc((void**)&h->loss_partial, 256 * 4 * sizeof(float)));
+        HIP_TRY(api_loss_partial(h));
         HIP_TRY(loss_sums(logp, regs, B, h->loss_partial, sums4, st));
     }
     const float lam[3] = {gc.reg_z ? lambdas[0] : 0.f, gc.reg_j ? lambdas[1] : 0.f, reg_aug ? lambdas[2] : 0.f};
@@ -481,32 +455,16 @@ int cnf_loss_grad_adaptive(cnf_handle* h, float t0, float t1, const float* x, co
                               mfma_plan_is_per_wave(h->plan) && gh->path == CNF_PATH_MFMA && gh->plan;
         srv = eligible ? gh : nullptr;
         if (eligible && !route.slab && mfma_plan_zr(h->plan) == mfma_plan_zr(gh->plan)) {
-            if (gh->num_cus == 0) {
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, gh->cfg.device_id));
-                gh->num_cus = prop.multiProcessorCount;
-            }
+            HIP_TRY(api_num_cus(gh));
             const FusedWs W = fused_ws(gh, CNF_ALG_TSIT5, kAdaptiveCkptSteps, B, true);
-            if (W.need > gh->grad.ws_bytes) {
-                if (gh->grad.ws) HIP_TRY(hipFree(gh->grad.ws));
-                gh->grad.ws = nullptr; gh->grad.ws_bytes = 0;
-                HIP_TRY(hipMalloc((void**)&gh->grad.ws, W.need));
-                gh->grad.ws_bytes = W.need;
-            }
+            HIP_TRY(gh->grad.ws.reserve(W.need_floats));
             ck.ckpt = gh->grad.ws; ck.ckpt_k = gh->grad.ws + W.ckpt_z_floats; ck.cap = kAdaptiveCkptSteps;
         } else if (eligible && route.slab) {
             // slab-accumulator gradient (its forward sweep is inside the kernel): the arrays sit behind the loss workspace of the
             // non-fused branch of loss_grad_impl, in the forward instance's layout, which the kernel reads with that stride
-            const size_t zslot = (size_t)((B + 15) / 16) * 64 * (size_t)mfma_plan_zr(h->plan);
-            const size_t head = ((size_t)gh->S + 4) * (size_t)B;
-            const size_t need = (head + (size_t)(7 * kAdaptiveCkptSteps + 1) * zslot) * sizeof(float);
-            if (need > gh->grad.ws_bytes) {
-                if (gh->grad.ws) HIP_TRY(hipFree(gh->grad.ws));
-                gh->grad.ws = nullptr; gh->grad.ws_bytes = 0;
-                HIP_TRY(hipMalloc((void**)&gh->grad.ws, need));
-                gh->grad.ws_bytes = need;
-            }
-            ck.ckpt = gh->grad.ws + head; ck.ckpt_k = ck.ckpt + (size_t)(kAdaptiveCkptSteps + 1) * zslot; ck.cap = kAdaptiveCkptSteps;
+            const SharedWs SW = shared_ws(gh, mfma_plan_zr(h->plan), CNF_ALG_TSIT5, kAdaptiveCkptSteps, B);
+            HIP_TRY(gh->grad.ws.reserve(SW.need_floats));
+            ck.ckpt = gh->grad.ws + SW.head; ck.ckpt_k = gh->grad.ws + SW.ckpt_k_off; ck.cap = kAdaptiveCkptSteps;
             slab_route = true;
         }
         HIP_TRY(assemble_u0(x, h->cfg.nvars, h->S, B, u, (hipStream_t)stream));

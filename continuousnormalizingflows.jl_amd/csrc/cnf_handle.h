@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "cnf_devbuf.h"
 #include "cnf_internal.h"
 
 namespace cnf {
@@ -31,8 +32,8 @@ int api_fail(int code, const std::string& msg);
 // With a map, cnf_set_params on a device pointer is one kernel on the caller's stream: no host round
 // trip and no synchronisation in a training loop that updates ps on the device every step.
 struct PackMap {
-    int* idx = nullptr;       // device, source parameter or -1 (zero padding)
-    float* scale = nullptr;   // device
+    DevBuf<int> idx;          // source parameter or -1 (zero padding)
+    DevBuf<float> scale;
     size_t n = 0;
     bool valid = false;
 };
@@ -59,57 +60,53 @@ namespace cnf {
 struct HandleParams {
     size_t n = 0;
     bool have = false;
-    float* P_dev = nullptr;              // Lux layout (SIMT path)
-    float* packed_dev = nullptr;         // MFMA operand image of the forward plan
+    DevBuf<float> P_dev;                 // Lux layout (SIMT path)
+    DevBuf<float> packed_dev;            // MFMA operand image of the forward plan
     std::vector<size_t> w_off, b_off;    // Lux offsets given to cnf_set_params
     // device-side repacking (see PackMap): the map of the solve image, rebuilt when the layout handed to cnf_set_params changes;
     // `stage` holds host-supplied parameters
     PackMap map_fwd;
     bool maps_built = false;
     bool repack_on_device = false;
-    float* stage = nullptr;
-    size_t stage_n = 0;
+    DevBuf<float> stage;
 };
 // thread-per-sample family: workspaces grown on demand
 struct HandleSimt {
-    float* ws = nullptr;
+    DevBuf<float> ws;
     int64_t ws_B = 0;
-    float* kbuf = nullptr;               // 6 stage derivatives + 1 state, each S x kbuf_B
+    DevBuf<float> kbuf;                  // 6 stage derivatives + 1 state, each S x kbuf_B
     int64_t kbuf_B = 0;
 };
 // parameter gradient (cnf_loss_grad_*): operand images, checkpoints, the auxiliary cooperative plan
 struct HandleGrad {
-    float* packed = nullptr;             // plain f32 operand image for the register-accumulator reverse sweep
-    float* ws = nullptr;                 // checkpoints + logp + regs
-    size_t ws_bytes = 0;
+    DevBuf<float> packed;                // plain f32 operand image for the register-accumulator reverse sweep
+    DevBuf<float> ws;                    // checkpoints + logp + regs
     PackMap map, map_slab;
-    float* slab_packed = nullptr;        // operand image of the slab-accumulator gradient kernel (cnf_grad_slab.hip)
-    float* slab_ws = nullptr;            // its checkpoints + slabs
-    size_t slab_ws_floats = 0;
+    DevBuf<float> slab_packed;           // operand image of the slab-accumulator gradient kernel (cnf_grad_slab.hip)
+    DevBuf<float> slab_ws;               // its checkpoints + slabs
     // Two-hidden-layer nets of 7 .. 8 hidden tiles keep their per-wave forward plan (the one-launch adaptive solvers hang off it),
     // but at large batches their gradient is faster on the cooperative reverse sweep: a second, cooperative plan + image for it
     MfmaPlan* plan_cg = nullptr;
-    float* cg_packed = nullptr;
+    DevBuf<float> cg_packed;
     PackMap map_cg;
     bool cg_tried = false;
     LayeredGrad* layered = nullptr;      // operand images + workspaces of the layer-wise evaluation / gradient and of the cooperative gradient
-    float* tgrid_dev = nullptr;          // step times of a non-uniform grid for the fused gradient kernels
-    size_t tgrid_cap = 0;
-    float* probe_ws = nullptr;           // several probes served probe by probe through the one-probe twin: one probe's columns, its
-    size_t probe_ws_floats = 0;          // gradient, data gradient and loss sums (cnf_api_grad.hip::loss_grad_probe_loop)
+    DevBuf<float> tgrid_dev;             // step times of a non-uniform grid for the fused gradient kernels
+    DevBuf<float> probe_ws;              // several probes served probe by probe through the one-probe twin: one probe's columns, its
+                                         // gradient, data gradient and loss sums (cnf_api_grad.hip::loss_grad_probe_loop)
 };
 // embedded-step workspace (cnf_step_embedded): 7 stage derivatives + 1 stage state, each S x B
 struct HandleEmbedded {
-    float* buf = nullptr;
-    int64_t B = 0;
+    DevBuf<float> buf;
+    int64_t B = 0;                       // columns the allocation holds: the stride of its slots
     int k[7] = {0, 1, 2, 3, 4, 5, 6};    // which slot holds k_1 .. k_7 (first-same-as-last swaps slots 0 and 6)
-    double* err_partial = nullptr;
+    DevBuf<double> err_partial;
 };
 // multistep solve (cnf_vcabm_*): 6 state-size vectors + 2 x kVcSlots difference vectors, each S x B
 struct HandleVcabm {
-    float* buf = nullptr;
-    double* partial = nullptr;
-    double* host_res = nullptr;          // 8 doubles of pinned host memory: the reduction kernels of the library's own policy loops write their
+    DevBuf<float> buf;
+    DevBuf<double> partial;
+    PinnedBuf<double> host_res;          // 8 doubles of pinned host memory: the reduction kernels of the library's own policy loops write their
                                          // sums there, so the loop synchronises and reads instead of copying (a small copy costs 25 us)
     int64_t B = -1, cap = 0;             // columns of the solve in progress; columns the allocation holds
     int iu = 0, iun = 2, ifn0 = 3, ifn1 = 5, cur = 0;   // which vector holds u, u_new, f_n, f_{n+1}; live difference half
@@ -121,12 +118,11 @@ struct HandleVcabm {
 // adaptive whole solves (cnf_solve_controller, cnf_solve_tsit5)
 struct HandleAdaptive {
     int last_controller = -1;
-    void* dc_buf = nullptr;              // device-controlled adaptive solve: slots, counter, stats, accepted steps
-    size_t dc_bytes = 0;
+    DevBuf<unsigned char> dc_buf;        // device-controlled adaptive solve: slots, counter, stats, accepted steps
     unsigned dc_epoch = 0;               // launches on dc_buf since it was allocated / last zeroed (mfma.hip::fill_aargs_scratch)
-    int* host_rec = nullptr;             // pinned host memory the one-launch solves write their status words and first steps into (AArgs::host_rec)
-    float* buf = nullptr;                // adaptive Tsit5 whole solve: two states + two derivative scratch vectors
-    int64_t B = 0;
+    PinnedBuf<int> host_rec;             // pinned host memory the one-launch solves write their status words and first steps into (AArgs::host_rec)
+    DevBuf<float> buf;                   // adaptive Tsit5 whole solve: two states + two derivative scratch vectors
+    int64_t B = 0;                       // columns the allocation holds: the stride of its slots
 };
 
 }  // namespace cnf
@@ -139,7 +135,7 @@ struct cnf_handle {
     int num_cus = 0;
     cnf::MfmaPlan* plan = nullptr;       // the fused forward plan (null on the SIMT / layer-wise paths)
     bool layered_forced = false;         // kernel_path = CNF_PATH_LAYERED given explicitly: GEMM path for every batch
-    float* loss_partial = nullptr;       // partial sums of the loss reduction (every family)
+    cnf::DevBuf<float> loss_partial;     // partial sums of the loss reduction (every family)
     cnf::HandleParams par;
     cnf::HandleSimt simt;
     cnf::HandleGrad grad;
@@ -159,6 +155,18 @@ struct cnf_handle {
 namespace cnf {
 
 // shared helpers of the three files
+// the augmented-dimension regulariser is live (Hutchinson modes only: the exact-trace dynamics carry no regularisers)
+inline int api_reg_aug(const cnf_handle* h) { return (h->cfg.mode != CNF_MODE_EXACT && h->cfg.reg_aug && h->cfg.naug > 0) ? 1 : 0; }
+// h->num_cus, asked of the device on first use
+inline hipError_t api_num_cus(cnf_handle* h) {
+    if (h->num_cus != 0) return hipSuccess;
+    hipDeviceProp_t prop;
+    const hipError_t e = hipGetDeviceProperties(&prop, h->cfg.device_id);
+    if (e == hipSuccess) h->num_cus = prop.multiProcessorCount;
+    return e;
+}
+// h->loss_partial, allocated on first use: 256 blocks x 4 sums
+inline hipError_t api_loss_partial(cnf_handle* h) { return h->loss_partial.reserve(256 * 4); }
 int api_check_call(cnf_handle* h, const float* eps, const float* ys, int64_t B, const char* who);
 // f(u + dt sum coef k, t) on whichever family serves the handle; `stage` is scratch for the fused path, whose single-call
 // kernel takes the stage state itself

@@ -41,6 +41,7 @@
 #include <string>
 #include <vector>
 
+#include "cnf_devbuf.h"
 #include "cnf_internal.h"
 #include "cnf_coop_grad.h"
 #include "cnf_tiles.h"
@@ -442,7 +443,7 @@ __global__ void finish_kernel(float* __restrict__ du, const float* __restrict__ 
 struct LgImage {
     long long rel, sm, sk;
     int M, K;
-    float* img = nullptr;
+    DevBuf<float> img;
     unsigned epoch = 0;
 };
 
@@ -450,23 +451,12 @@ struct LayeredGrad {
     std::vector<LgImage> images;
     unsigned epoch = 1;           // bumped whenever PA is rebuilt: stale images are repacked at their next use
     int num_cus = 0;
-    float* ws = nullptr;          // gradient workspace
-    size_t ws_floats = 0;
-    float* ws_fwd = nullptr;      // forward-evaluation workspace (the gradient calls the forward for the loss)
-    size_t ws_fwd_floats = 0;
-    float* ws_store = nullptr;    // the stage store of the cooperative gradient's second form (cnf_tiles.h): h_l, delta_l of every stage
-    size_t ws_store_floats = 0;
+    DevBuf<float> ws;             // gradient workspace
+    DevBuf<float> ws_fwd;         // forward-evaluation workspace (the gradient calls the forward for the loss)
+    DevBuf<float> ws_store;       // the stage store of the cooperative gradient's second form (cnf_tiles.h): h_l, delta_l of every stage
 };
 
-void layered_grad_destroy(LayeredGrad* g) {
-    if (!g) return;
-    for (LgImage& im : g->images)
-        if (im.img) (void)hipFree(im.img);
-    if (g->ws) (void)hipFree(g->ws);
-    if (g->ws_fwd) (void)hipFree(g->ws_fwd);
-    if (g->ws_store) (void)hipFree(g->ws_store);
-    delete g;
-}
+void layered_grad_destroy(LayeredGrad* g) { delete g; }
 
 bool layered_grad_supported(const cnf_config& c) {
     return c.mode == CNF_MODE_EXACT || ((c.mode == CNF_MODE_HUTCH_VJP || c.mode == CNF_MODE_HUTCH_JVP) && c.nprobes >= 1);
@@ -478,6 +468,47 @@ bool layered_grad_supported(const cnf_config& c) {
         if (_e != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(_e); return _e; } \
     } while (0)
 #define LG_BLAS(expr) LG_HIP(expr)
+
+// G.num_cus of the current device, asked on first use
+static hipError_t lg_num_cus(LayeredGrad& G, std::string* err) {
+    if (G.num_cus != 0) return hipSuccess;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    LG_HIP(hipGetDevice(&dev));
+    LG_HIP(hipGetDeviceProperties(&prop, dev));
+    G.num_cus = prop.multiProcessorCount;
+    return hipSuccess;
+}
+
+// the Dense chain of `c` with its Lux offsets; [W_l | b_l] blocks back to back in the augmented parameter buffer
+static LDesc make_ldesc(const cnf_config& c, const size_t* w_off, const size_t* b_off) {
+    LDesc L{};
+    L.n_layers = c.n_layers;
+    long long npa = 0;
+    for (int l = 0; l < c.n_layers; ++l) {
+        L.win[l] = c.widths[l]; L.wout[l] = c.widths[l + 1]; L.act[l] = c.acts[l];
+        L.pa_off[l] = npa; L.w_off[l] = (long long)w_off[l]; L.b_off[l] = (long long)b_off[l];
+        npa += (long long)L.wout[l] * (L.win[l] + 1);
+    }
+    L.npa = npa;
+    return L;
+}
+static int max_width(const LDesc& L, int D) {
+    int maxw = D;
+    for (int l = 0; l < L.n_layers; ++l)
+        if (L.wout[l] > maxw) maxw = L.wout[l];
+    return maxw;
+}
+
+// carves a workspace into arrays that start on 64-float boundaries: take(n) is the offset of the next one, `off` the floats taken so far
+struct Carver {
+    long long off = 0;
+    long long operator()(long long n) {
+        const long long o = off;
+        off += (n + 63) / 64 * 64;
+        return o;
+    }
+};
 
 // every product of the chain (forward, transposed, weight cotangent) fits one launch of the kernels in cnf_lgemm.hip
 bool layered_available() { return true; }
@@ -505,13 +536,13 @@ static hipError_t lg_image(LayeredGrad& G, const float* PA, long long rel, long 
     }
     LgImage im;
     im.rel = rel; im.sm = sm; im.sk = sk; im.M = M; im.K = K;
-    hipError_t e = hipMalloc((void**)&im.img, lg_image_floats(M, K) * sizeof(float));
+    hipError_t e = im.img.reserve(lg_image_floats(M, K));
     if (e != hipSuccess) return e;
     e = lg_pack_image(PA + rel, sm, sk, M, K, im.img, st);
-    if (e != hipSuccess) { (void)hipFree(im.img); return e; }
+    if (e != hipSuccess) return e;
     im.epoch = G.epoch;
-    G.images.push_back(im);
     *out = im.img;
+    G.images.push_back(std::move(im));
     return hipSuccess;
 }
 
@@ -547,19 +578,10 @@ hipError_t layered_aug_f(LayeredGrad** ctx, const cnf_config& c, const float* P_
     LayeredGrad& G = **ctx;
     const int N = c.n_layers, D = c.nvars + c.naug, C = c.ncond, S = D + 3;
     const int K = c.mode == CNF_MODE_EXACT ? 1 : c.nprobes;
-    LDesc L{};
-    L.n_layers = N;
-    long long npa = 0;
-    int maxw = D;
-    for (int l = 0; l < N; ++l) {
-        L.win[l] = c.widths[l]; L.wout[l] = c.widths[l + 1]; L.act[l] = c.acts[l];
-        L.pa_off[l] = npa; L.w_off[l] = (long long)w_off[l]; L.b_off[l] = (long long)b_off[l];
-        npa += (long long)L.wout[l] * (L.win[l] + 1);
-        if (L.wout[l] > maxw) maxw = L.wout[l];
-    }
-    L.npa = npa;
-    long long off = 0;
-    auto take = [&](long long n) { const long long o = off; off += (n + 63) / 64 * 64; return o; };
+    const LDesc L = make_ldesc(c, w_off, b_off);
+    const long long npa = L.npa;
+    const int maxw = max_width(L, D);
+    Carver take;
     const long long o_PA = take(npa);
     const bool use_q = c.mode == CNF_MODE_EXACT && N == 3 && c.acts[2] == CNF_ACT_IDENTITY;   // two hidden layers
     const long long o_Q = take(use_q ? (long long)L.wout[0] * L.wout[1] : 0);
@@ -568,13 +590,8 @@ hipError_t layered_aug_f(LayeredGrad** ctx, const cnf_config& c, const float* P_
     for (int l = 0; l < N; ++l) { o_a[l + 1] = take((long long)(L.wout[l] + 1) * B); o_d[l] = take((long long)L.wout[l] * B); }
     const long long WB = (long long)maxw * B;
     const long long o_t0 = take(WB), o_t1 = take(WB), o_ld = take(B), o_nd = take(B), o_row = take(B);
-    const bool grown = (size_t)off > G.ws_fwd_floats;
-    if (grown) {
-        if (G.ws_fwd) LG_HIP(hipFree(G.ws_fwd));
-        G.ws_fwd = nullptr; G.ws_fwd_floats = 0;
-        LG_HIP(hipMalloc((void**)&G.ws_fwd, (size_t)off * sizeof(float)));
-        G.ws_fwd_floats = (size_t)off;
-    }
+    bool grown = false;   // a workspace that moved has lost its parameter image
+    LG_HIP(G.ws_fwd.reserve((size_t)take.off, &grown));
     float* W = G.ws_fwd;
     float* PA = W + o_PA;
     float *a[CNF_MAX_LAYERS + 1], *d[CNF_MAX_LAYERS];
@@ -677,29 +694,15 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
         }
     if (!*ctx) *ctx = new LayeredGrad();
     LayeredGrad& G = **ctx;
-    if (G.num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        LG_HIP(hipGetDevice(&dev));
-        LG_HIP(hipGetDeviceProperties(&prop, dev));
-        G.num_cus = prop.multiProcessorCount;
-    }
+    if (hipError_t e = lg_num_cus(G, err)) return e;
 
     // TestMode (icnf.jl:297-339): ldot = -tr J = -sum_k e_k^T J e_k - the pullback below with the D unit vectors as
     // probes, each with weight 1 (what the reference's AD does through its D one-hot passes)
     const bool exact = c.mode == CNF_MODE_EXACT;
     const int N = c.n_layers, D = c.nvars + c.naug, C = c.ncond, K = exact ? D : c.nprobes;
-    LDesc L{};
-    L.n_layers = N;
-    long long npa = 0;
-    int maxw = D;
-    for (int l = 0; l < N; ++l) {
-        L.win[l] = c.widths[l]; L.wout[l] = c.widths[l + 1]; L.act[l] = c.acts[l];
-        L.pa_off[l] = npa; L.w_off[l] = (long long)w_off[l]; L.b_off[l] = (long long)b_off[l];
-        npa += (long long)L.wout[l] * (L.win[l] + 1);
-        if (L.wout[l] > maxw) maxw = L.wout[l];
-    }
-    L.npa = npa;
+    const LDesc L = make_ldesc(c, w_off, b_off);
+    const long long npa = L.npa;
+    const int maxw = max_width(L, D);
     const long long npa_pad = (npa + 63) / 64 * 64;
     // sample chunks of the weight-cotangent products: one slab per chunk, each chunk's strip of C accumulated in registers
     // (cnf_lgemm.hip); CNF_LAYERED_KC overrides the chunk length
@@ -709,8 +712,7 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
 
     // ---- workspace ----
     const long long DB = (long long)D * B;
-    long long off = 0;
-    auto take = [&](long long n) { const long long o = off; off += (n + 63) / 64 * 64; return o; };
+    Carver take;
     const long long o_PA = take(npa_pad), o_slab = take(npa_pad * nslab), o_zck = take(DB * (nsteps + 1));
     // stage derivatives of every step are kept when they fit 4 GiB, otherwise recomputed in the reverse sweep
     const int nst = alg == CNF_ALG_RK4 ? 4 : 6;
@@ -731,7 +733,7 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     if (keep_act) {   // ... and half of what the device has free (counting the workspace this context already holds)
         size_t mfree = 0, mtotal = 0;
         if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
-        const double avail = (double)mfree + (double)G.ws_floats * sizeof(float);
+        const double avail = (double)mfree + (double)G.ws.capacity() * sizeof(float);
         if ((double)act_stage * nst * nsteps * sizeof(float) > 0.5 * avail) keep_act = false;
     }
     const long long o_actck = keep_act ? take(act_stage * nst * nsteps) : 0;
@@ -751,12 +753,7 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     const long long o_t0 = take(WB), o_t1 = take(WB), o_t2 = take(WB), o_t3 = take(WB), o_t4 = take(WB);
     long long o_z[CNF_MAX_LAYERS];   // pre-activations of the swish / GELU layers (recomputing mode; nothing for other layers)
     for (int l = 0; l < N; ++l) o_z[l] = act_dd_needs_pre(L.act[l]) && !keep_act ? take((long long)L.wout[l] * B) : -1;
-    if ((size_t)off > G.ws_floats) {
-        if (G.ws) LG_HIP(hipFree(G.ws));
-        G.ws = nullptr; G.ws_floats = 0;
-        LG_HIP(hipMalloc((void**)&G.ws, (size_t)off * sizeof(float)));
-        G.ws_floats = (size_t)off;
-    }
+    LG_HIP(G.ws.reserve((size_t)take.off));
     float* W = G.ws;
     float* PA = W + o_PA;
     float* slabs = W + o_slab;
@@ -1071,16 +1068,9 @@ int coop_grad_stage_store_tiles(const cnf_config& c, MfmaPlan* plan, long long B
 static hipError_t coop_grad3_run(LayeredGrad& G, const cnf_config& c, MfmaPlan* plan, const float* packed_dev, const size_t* w_off, const size_t* b_off,
                                  const float* x, const float* eps, const float* ys, int alg, int nsteps, float t0, float t1, long long B, const float lam[3],
                                  float* grad, float* grad_x, float* logp_out, float* regs_out, int HT, int Lh, int ZR, int ACT, int HTs, hipStream_t st, std::string* err) {
-    const int N = c.n_layers, D = c.nvars + c.naug, H = c.widths[1], n_in = c.widths[0];
-    LDesc L{};
-    L.n_layers = N;
-    long long npa = 0;
-    for (int l = 0; l < N; ++l) {
-        L.win[l] = c.widths[l]; L.wout[l] = c.widths[l + 1]; L.act[l] = c.acts[l];
-        L.pa_off[l] = npa; L.w_off[l] = (long long)w_off[l]; L.b_off[l] = (long long)b_off[l];
-        npa += (long long)L.wout[l] * (L.win[l] + 1);
-    }
-    L.npa = npa;
+    const int D = c.nvars + c.naug, H = c.widths[1], n_in = c.widths[0];
+    const LDesc L = make_ldesc(c, w_off, b_off);
+    const long long npa = L.npa;
     const long long npa_pad = (npa + 63) / 64 * 64;
     const Tableau T = make_tableau(alg);
     const int ns = T.ns;
@@ -1093,14 +1083,8 @@ static hipError_t coop_grad3_run(LayeredGrad& G, const cnf_config& c, MfmaPlan* 
               ncN = wgrad_tiles_chunks(D, H, nct, G.num_cus, &chN);
     const int nslab = std::max(nc1, std::max(ncH, ncN));
     StageStore S{Lh, nsteps, ns, HTs, ntp};
-    if ((size_t)S.total() > G.ws_store_floats) {
-        if (G.ws_store) LG_HIP(hipFree(G.ws_store));
-        G.ws_store = nullptr; G.ws_store_floats = 0;
-        LG_HIP(hipMalloc((void**)&G.ws_store, (size_t)S.total() * sizeof(float)));
-        G.ws_store_floats = (size_t)S.total();
-    }
-    long long off = 0;
-    auto take = [&](long long n) { const long long o = off; off += (n + 63) / 64 * 64; return o; };
+    LG_HIP(G.ws_store.reserve((size_t)S.total()));
+    Carver take;
     const long long o_slab = take(npa_pad * nslab);
     const long long o_zck = take((long long)(nsteps + 1) * ntp * 64 * ZR), o_kck = take((long long)nsteps * ns * ntp * 64 * ZR);
     const long long o_gck = lam[1] != 0.f ? take((long long)nsteps * ns * ntp * 64 * ZR) : 0;
@@ -1109,12 +1093,7 @@ static hipError_t coop_grad3_run(LayeredGrad& G, const cnf_config& c, MfmaPlan* 
     long long o_sv[3], o_ss[3];
     for (int l = 0; l < Lh; ++l) { o_sv[l] = take(nct * HTs * 256); o_ss[l] = take(nct * HTs * 256); }
     const long long o_gb = take(nct * DTZ * 256), o_zt = take(nct * DTZ * 256), o_ep = take(nct * DT * 256), o_kb = take(nct * DT * 256);
-    if ((size_t)off > G.ws_floats) {
-        if (G.ws) LG_HIP(hipFree(G.ws));
-        G.ws = nullptr; G.ws_floats = 0;
-        LG_HIP(hipMalloc((void**)&G.ws, (size_t)off * sizeof(float)));
-        G.ws_floats = (size_t)off;
-    }
+    LG_HIP(G.ws.reserve((size_t)take.off));
     float* W = G.ws;
     float* slabs = W + o_slab;
     LG_HIP(zero_async(slabs, (size_t)npa_pad * nslab * sizeof(float), st));
@@ -1181,25 +1160,12 @@ hipError_t coop_grad(LayeredGrad** ctx, const cnf_config& c, MfmaPlan* plan, con
     if (!mfma_plan_coop_grad_shape(plan, &HT, &Lh, &ZR, &ACT, &CR)) { *err = "coop_grad: not a cooperative plan"; return hipErrorNotSupported; }
     if (!*ctx) *ctx = new LayeredGrad();
     LayeredGrad& G = **ctx;
-    if (G.num_cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        LG_HIP(hipGetDevice(&dev));
-        LG_HIP(hipGetDeviceProperties(&prop, dev));
-        G.num_cus = prop.multiProcessorCount;
-    }
+    if (hipError_t e = lg_num_cus(G, err)) return e;
     if (const int HTs = coop_grad_stage_store_tiles(c, plan, B, alg, nsteps, tgrid != nullptr))
         return coop_grad3_run(G, c, plan, packed_dev, w_off, b_off, x, eps, ys, alg, nsteps, t0, t1, B, lam, grad, grad_x, logp_out, regs_out, HT, Lh, ZR, ACT, HTs, st, err);
-    const int N = c.n_layers, D = c.nvars + c.naug, H = c.widths[1], n_in = c.widths[0];
-    LDesc L{};
-    L.n_layers = N;
-    long long npa = 0;
-    for (int l = 0; l < N; ++l) {
-        L.win[l] = c.widths[l]; L.wout[l] = c.widths[l + 1]; L.act[l] = c.acts[l];
-        L.pa_off[l] = npa; L.w_off[l] = (long long)w_off[l]; L.b_off[l] = (long long)b_off[l];
-        npa += (long long)L.wout[l] * (L.win[l] + 1);
-    }
-    L.npa = npa;
+    const int D = c.nvars + c.naug, H = c.widths[1], n_in = c.widths[0];
+    const LDesc L = make_ldesc(c, w_off, b_off);
+    const long long npa = L.npa;
     const long long npa_pad = (npa + 63) / 64 * 64;
     const Tableau T = make_tableau(alg);
     const int ns = T.ns;
@@ -1217,8 +1183,7 @@ hipError_t coop_grad(LayeredGrad** ctx, const cnf_config& c, MfmaPlan* plan, con
     const int slots = coop_grad_scratch_slots(Lh);
     const long long scratch_stride = (long long)(slots > 0 ? slots : 1) * HT * 256 * cg_nt;   // slots x (HT tiles x NT sample tiles x 64 lanes x 4) floats
 
-    long long off = 0;
-    auto take = [&](long long n) { const long long o = off; off += (n + 63) / 64 * 64; return o; };
+    Carver take;
     const long long o_slab = take(npa_pad * nslab), o_slabN = take(szN_pad * nslabN);
     const long long o_zck = take((long long)(nsteps + 1) * ntp * 64 * ZR), o_kck = take((long long)nsteps * ns * ntp * 64 * ZR);
     const long long o_gck = lam[1] != 0.f ? take((long long)nsteps * ns * ntp * 64 * ZR) : 0;
@@ -1229,12 +1194,7 @@ hipError_t coop_grad(LayeredGrad** ctx, const cnf_config& c, MfmaPlan* plan, con
     long long o_xh[3], o_yh[3];
     for (int l = 0; l < Lh; ++l) { o_xh[l] = take((long long)H * B2); o_yh[l] = take((long long)ldy * B2); }
     const long long o_y1 = take((long long)(n_in + 1) * B2), o_xN = take((long long)D * B2);
-    if ((size_t)off > G.ws_floats) {
-        if (G.ws) LG_HIP(hipFree(G.ws));
-        G.ws = nullptr; G.ws_floats = 0;
-        LG_HIP(hipMalloc((void**)&G.ws, (size_t)off * sizeof(float)));
-        G.ws_floats = (size_t)off;
-    }
+    LG_HIP(G.ws.reserve((size_t)take.off));
     float* W = G.ws;
     float* slabs = W + o_slab;
     LG_HIP(zero_async(slabs, (size_t)npa_pad * nslab * sizeof(float), st));

@@ -22,6 +22,7 @@
 #include <vector>
 
 #define CNF_WITH_DEVICE_CONTROLLER 1
+#include "cnf_devbuf.h"
 #include "cnf_mfma_kernel.h"
 #include "cnf_coop_grad.h"
 
@@ -47,8 +48,8 @@ struct MfmaPlan {
     float fwd_scale;    // factor folded into the forward hidden-layer images/biases (pre-scaled tanh)
     int prio_mode;      // see KArgs
     int use_queue;
-    int* queue_dev;     // one int per plan, zeroed on the stream before every launch
-    float* rk_dev = nullptr;   // ring of the Runge-Kutta sums of cnf_coop_d2.hip's 20 .. 24-tile instances (KArgs::rk), allocated on first use
+    DevBuf<int> queue_dev;     // one int per plan, allocated on first use, zeroed on the stream before every launch
+    DevBuf<float> rk_dev;      // ring of the Runge-Kutta sums of cnf_coop_d2.hip's 20 .. 24-tile instances (KArgs::rk), allocated on first use
     int pre = 0;        // the instance's hoisting level (2: the trace term as a dot with q = W_1 eps where |eps^T J| is not asked for)
     int q_extra = 0;    // extended cooperative plans of two-hidden-layer exact-trace flows: float offset of the Q image appended
                         // behind the layout (0 = none); per-wave plans carry theirs inside the layout (lay.qtr)
@@ -124,7 +125,7 @@ static MfmaPlan* mfma_plan_create_impl(const cnf_config& c, bool coop_only) {
         p->cfg = c;
         p->nthreads = 256;
         p->num_cus = 0;
-        p->prio_mode = 0; p->use_queue = 0; p->queue_dev = nullptr;
+        p->prio_mode = 0; p->use_queue = 0;
         p->kind = 1;
         p->arith = 0;
         p->fwd_scale = c.acts[0] == CNF_ACT_TANH ? kTanhPrescale : 1.f;   // cnf_coop.hip runs pre-scaled tanh
@@ -150,7 +151,6 @@ static MfmaPlan* mfma_plan_create_impl(const cnf_config& c, bool coop_only) {
         p->num_cus = 0;
         p->prio_mode = tuning().mfma_prio;
         p->use_queue = tuning().mfma_queue;
-        p->queue_dev = nullptr;
         p->kind = 0;
         snprintf(p->name, sizeof(p->name), "mfma_%s<HT=%d,L=%d,ZR=%d,CR=%d,act=%d,K=%d,pre=%d,nt=%d,%s>",
                  engine == ENG_VJP ? "vjp" : "tan", HT, L, in.ZR, in.CR, in.ACT, KP, in.PRE, in.nthreads,
@@ -225,7 +225,7 @@ static MfmaPlan* mfma_plan_create_impl(const cnf_config& c, bool coop_only) {
     p->lay = MfmaLayout(hti, L, zri, cri, true);
     p->launch = nullptr; p->launch_adapt = nullptr; p->launch_vcabm = nullptr;
     p->cfg = c;
-    p->nthreads = 256; p->num_cus = 0; p->prio_mode = 0; p->use_queue = 0; p->queue_dev = nullptr;
+    p->nthreads = 256; p->num_cus = 0; p->prio_mode = 0; p->use_queue = 0;
     p->kind = 2; p->arith = 0;
     // two hidden layers, exact trace: tr J = act'_2^T Q act'_1 - ONE H x H product per evaluation (the Q image sits behind the layout)
     p->q_extra = (exact && L == 2) ? p->lay.total : 0;
@@ -237,7 +237,7 @@ static MfmaPlan* mfma_plan_create_impl(const cnf_config& c, bool coop_only) {
 
 static hipError_t plan_ensure_cus(MfmaPlan* mp);
 // The ring of the Runge-Kutta sums some dealt instances keep in device memory (KArgs::rk) is allocated with the plan where a
-// device is current, so that the first solve - which may run under stream capture, where hipMalloc is not allowed - finds it;
+// device is current, so that the first solve - which may run under stream capture, where allocating is not allowed - finds it;
 // mfma_solve still allocates it on first use otherwise.
 MfmaPlan* mfma_plan_create(const cnf_config& c, bool coop_only) {
     MfmaPlan* p = mfma_plan_create_impl(c, coop_only);
@@ -246,16 +246,12 @@ MfmaPlan* mfma_plan_create(const cnf_config& c, bool coop_only) {
         for (int l = 1; l < c.n_layers; ++l) hmax = c.widths[l] > hmax ? c.widths[l] : hmax;
         const size_t a = coopd_rk_floats(hmax, c.nvars + c.naug, p->L, p->ACT, 0, p->num_cus), b = coopd_rk_floats(hmax, c.nvars + c.naug, p->L, p->ACT, 1, p->num_cus);
         const size_t rkf = a > b ? a : b;
-        if (rkf && hipMalloc((void**)&p->rk_dev, rkf * sizeof(float)) != hipSuccess) { p->rk_dev = nullptr; (void)hipGetLastError(); }
+        if (rkf && p->rk_dev.reserve(rkf) != hipSuccess) (void)hipGetLastError();
     }
     return p;
 }
 
-void mfma_plan_destroy(MfmaPlan* p) {
-    if (p && p->queue_dev) (void)hipFree(p->queue_dev);
-    if (p && p->rk_dev) (void)hipFree(p->rk_dev);
-    delete p;
-}
+void mfma_plan_destroy(MfmaPlan* p) { delete p; }
 size_t mfma_packed_bytes(const MfmaPlan* p) {
     return ((size_t)p->lay.total + (p->q_extra ? (size_t)MfmaLayout::imgA(p->lay.HT, p->lay.HT) : 0)) * sizeof(float);
 }
@@ -570,11 +566,9 @@ hipError_t mfma_solve(MfmaPlan* p, const float* packed_dev, const SolveArgs& s, 
     a.prio_mode = p->prio_mode;
     a.queue = nullptr;
     if (mp->use_queue) {
-        if (!mp->queue_dev) {
-            hipError_t e = hipMalloc((void**)&mp->queue_dev, sizeof(int));
-            if (e != hipSuccess) return e;
-        }
-        hipError_t e = zero_async(mp->queue_dev, sizeof(int), st);
+        hipError_t e = mp->queue_dev.reserve(1);
+        if (e != hipSuccess) return e;
+        e = zero_async(mp->queue_dev, sizeof(int), st);
         if (e != hipSuccess) return e;
         a.queue = mp->queue_dev;
     }
@@ -586,8 +580,8 @@ hipError_t mfma_solve(MfmaPlan* p, const float* packed_dev, const SolveArgs& s, 
             int hmax = 0;
             for (int l = 1; l < p->cfg.n_layers; ++l) hmax = p->cfg.widths[l] > hmax ? p->cfg.widths[l] : hmax;
             const size_t rkf = coopd_rk_floats(hmax, a.D, p->L, p->ACT, a.exact == 1, mp->num_cus);
-            if (rkf && !mp->rk_dev) {
-                hipError_t e = hipMalloc((void**)&mp->rk_dev, rkf * sizeof(float));
+            if (rkf && !mp->rk_dev) {   // (allocated once, by mfma_plan_create where a device was current)
+                hipError_t e = mp->rk_dev.reserve(rkf);
                 if (e != hipSuccess) return e;
             }
             a.rk = mp->rk_dev;
@@ -600,7 +594,7 @@ hipError_t mfma_solve(MfmaPlan* p, const float* packed_dev, const SolveArgs& s, 
         for (int l = 1; l < p->cfg.n_layers; ++l) hmax = p->cfg.widths[l] > hmax ? p->cfg.widths[l] : hmax;
         const size_t rkf = coopd_rk_floats(hmax, a.D, p->L, p->ACT, 0, mp->num_cus);
         if (rkf && !mp->rk_dev) {
-            hipError_t e = hipMalloc((void**)&mp->rk_dev, rkf * sizeof(float));
+            hipError_t e = mp->rk_dev.reserve(rkf);
             if (e != hipSuccess) return e;
         }
         a.rk = mp->rk_dev;
