@@ -82,8 +82,7 @@ class _MLJICNF:
         ic = self.icnf
         if ic.conditioned != self._conditioned:
             raise TypeError("MethodError: ICNFModel needs an unconditioned flow, CondICNFModel a conditioned one")
-        if self.loss is not None and self.loss is not _icnf.loss:
-            raise NotImplementedError("a custom loss has no gradient kernel; fit optimises the package's `loss`")
+        custom = self.loss is not None and self.loss is not _icnf.loss
         ps, st = _icnf.setup(self.init_rng, ic)
         ps = ps.to(ic.device)
         # Optimisers.OptimiserChain(WeightDecay(lambda), Adam(eta, beta, epsilon)): the decay term lambda * p is
@@ -96,7 +95,18 @@ class _MLJICNF:
             for idx in epoch_batches(n, self.batchsize, self.shuffle_rng):
                 idx = idx.to(x.device)
                 args = (x[:, idx],) + ((y[:, idx],) if y is not None else ()) + (ps, st)
-                value, grad = _icnf.loss_and_gradient(ic, mode, *args)
+                if custom:
+                    # a user's loss is differentiated by torch through the solve (inference(..., differentiable=True) inside it)
+                    ps.requires_grad_(True)
+                    value = self.loss(ic, mode, *args)
+                    if not isinstance(value, torch.Tensor) or value.grad_fn is None:
+                        raise TypeError("the custom loss returned a value without an autograd graph: build it on "
+                                        "inference(..., differentiable=True) (or generate(..., differentiable=True))")
+                    grad, = torch.autograd.grad(value, ps)
+                    ps.requires_grad_(False)
+                    value = value.detach()
+                else:
+                    value, grad = _icnf.loss_and_gradient(ic, mode, *args)
                 ps.grad = grad
                 opt.step()
                 it += 1

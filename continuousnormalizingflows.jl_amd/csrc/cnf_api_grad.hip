@@ -491,3 +491,106 @@ int cnf_loss_grad_adaptive(cnf_handle* h, float t0, float t1, const float* x, co
 }
 
 }  // extern "C"
+
+// ---- the pullback of base_sol (cnf_integrate_fixed_vjp / cnf_integrate_grid_vjp) ------------------------------------------------------
+// The reverse sweeps above with the terminal costate and the cotangents of the dlogp / E / n rows taken from the caller (u1_bar)
+// instead of from z_N and the three lambdas.  Two implementations: the fused per-wave sweep in its cotangent form (cnf_grad2_cot.hip)
+// for the one-probe VJP shapes of cnf_grad.hip's table, the layer-wise sweep (cnf_layered.hip) for every other Dense chain - JVP mode,
+// several probes, the exact trace, the slab and cooperative shapes (their kernels have no cotangent form).  Nothing is kept in the
+// handle between calls beyond workspace capacity.
+static int vjp_route(const cnf_handle* h) {
+    const cnf_config& c = h->cfg;
+    if (api_grad_is_fused(h) && (h->grad.packed || !h->par.have) && c.mode == CNF_MODE_HUTCH_VJP && c.nprobes == 1) return 1;
+    return (layered_grad_supported(c) && layered_supports(c)) ? 2 : 0;
+}
+
+static int integrate_vjp_impl(cnf_handle* h, const char* who, int alg, int nsteps, float t0, float t1, const float* tgrid, const float* u0,
+                              const float* eps, const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1,
+                              void* stream) {
+    int rc = api_check_call(h, eps, ys, B, who);
+    if (rc) return rc;
+    const std::string w(who);
+    if (nsteps < 1) return fail(CNF_ERR_INVALID, w + ": nsteps >= 1 required");
+    if (alg != CNF_ALG_RK4 && alg != CNF_ALG_TSIT5) return fail(CNF_ERR_INVALID, w + ": unknown alg");
+    if ((B > 0 && (!u0 || !u1_bar)) || !grad) return fail(CNF_ERR_INVALID, w + ": null u0/u1_bar/grad");
+    if (B > 0 && ((u0_bar && (u0_bar == u0 || u0_bar == u1_bar || u0_bar == u1)) || (u1 && (u1 == u0 || u1 == u1_bar))))
+        return fail(CNF_ERR_INVALID, w + ": u0_bar / u1 may not alias u0, u1_bar or each other");
+    const int path = vjp_route(h);
+    if (path == 0) return fail(CNF_ERR_UNSUPPORTED, w + ": no pullback for this configuration (a layer wider than the product kernels cover)");
+    DeviceGuard g(h->cfg.device_id);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(zero_async(grad, h->par.n * sizeof(float), st));
+    if (B == 0) return CNF_OK;
+    const bool hutch = h->cfg.mode != CNF_MODE_EXACT;   // the exact-trace dynamics carry no regularisers: their rows are identically zero
+    const float sw[3] = {hutch && h->cfg.reg_z ? 1.f : 0.f, hutch && h->cfg.reg_j ? 1.f : 0.f, 0.f};
+    if (tgrid) { t0 = tgrid[0]; t1 = tgrid[nsteps]; }
+    if (path == 2) {
+        std::string msg;
+        const LayeredCot cot{u0, u1_bar, u0_bar, u1};
+        hipError_t e = layered_grad(&h->grad.layered, h->cfg, h->par.P_dev, h->par.w_off.data(), h->par.b_off.data(), nullptr, eps, ys, alg, nsteps,
+                                    t0, t1, tgrid, B, sw, grad, nullptr, st, &msg, nullptr, nullptr, &cot);
+        if (e == hipErrorNotSupported) return fail(CNF_ERR_UNSUPPORTED, w + ": " + msg);
+        if (e != hipSuccess) return fail(CNF_ERR_HIP, w + ": " + msg);
+        return CNF_OK;
+    }
+    const float* tgrid_dev = nullptr;
+    if (tgrid) {
+        HIP_TRY(h->grad.tgrid_dev.reserve(((size_t)nsteps + 1 + 63) / 64 * 64));
+        HIP_TRY(hipMemcpyAsync(h->grad.tgrid_dev, tgrid, ((size_t)nsteps + 1) * sizeof(float), hipMemcpyHostToDevice, st));
+        tgrid_dev = h->grad.tgrid_dev;
+    }
+    HIP_TRY(api_num_cus(h));
+    const long long ntiles = (B + 15) / 16;
+    const int ckpt_zr = mfma_plan_zr(h->plan);
+    const int nstages = alg == CNF_ALG_RK4 ? 4 : 6;
+    const FusedWs W = fused_ws(h, alg, nsteps, B, tgrid != nullptr);
+    HIP_TRY(h->grad.ws.reserve(W.need_floats));
+    float* ckpt = h->grad.ws;
+    float* ckpt_k = ckpt + W.ckpt_z_floats;
+    float* slab = ckpt + W.ckpt_z_floats + W.ckpt_k_floats + 4 * (size_t)B;
+    // the checkpointing forward solve from the caller's full state (reg_aug = 0: no epilogue here, as in cnf_integrate_fixed)
+    if (!tgrid) {
+        SolveArgs a{};
+        a.u0 = u0; a.u_out = u1; a.eps = eps; a.ys = ys; a.B = B; a.nsteps = nsteps; a.alg = alg; a.t0 = t0; a.t1 = t1;
+        a.nvars = h->cfg.nvars; a.ckpt = ckpt; a.ckpt_k = ckpt_k;
+        HIP_TRY(mfma_solve(h->plan, h->par.packed_dev, a, st));
+    } else {
+        float* ua = slab + W.slab_floats;
+        float* ub = ua + (size_t)h->S * (size_t)B;
+        const size_t zslot = (size_t)ntiles * 64 * (size_t)ckpt_zr;
+        const float* from = u0;
+        for (int n = 0; n < nsteps; ++n) {
+            float* to = (n == nsteps - 1 && u1) ? u1 : (from == ua ? ub : ua);
+            SolveArgs a{};
+            a.u0 = from; a.u_out = to; a.eps = eps; a.ys = ys; a.B = B; a.nsteps = 1; a.alg = alg; a.t0 = tgrid[n]; a.t1 = tgrid[n + 1];
+            a.nvars = h->cfg.nvars;
+            a.ckpt = ckpt + (size_t)n * zslot; a.ckpt_k = ckpt_k + (size_t)n * nstages * zslot;
+            HIP_TRY(mfma_solve(h->plan, h->par.packed_dev, a, st));
+            from = to;
+        }
+    }
+    HIP_TRY(grad_launch(api_grad_cfg(h), h->grad.packed, ckpt, ckpt_k, ckpt_zr, eps, ys, h->par.w_off.data(), h->par.b_off.data(), alg, nsteps, t0, t1,
+                        tgrid_dev, 0.f, B, sw, slab, grad, nullptr, h->num_cus, st, u1_bar, u0_bar));
+    return CNF_OK;
+}
+
+extern "C" {
+
+int cnf_integrate_fixed_vjp(cnf_handle* h, int alg, int nsteps, float t0, float t1, const float* u0, const float* eps, const float* ys,
+                            int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1, void* stream) {
+    return integrate_vjp_impl(h, "cnf_integrate_fixed_vjp", alg, nsteps, t0, t1, nullptr, u0, eps, ys, B, u1_bar, grad, u0_bar, u1, stream);
+}
+
+int cnf_integrate_grid_vjp(cnf_handle* h, int alg, int nsteps, const float* tgrid, const float* u0, const float* eps, const float* ys,
+                           int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1, void* stream) {
+    if (nsteps < 1 || !tgrid) return fail(CNF_ERR_INVALID, "cnf_integrate_grid_vjp: nsteps >= 1 and a grid of nsteps + 1 times required");
+    return integrate_vjp_impl(h, "cnf_integrate_grid_vjp", alg, nsteps, 0.f, 0.f, tgrid, u0, eps, ys, B, u1_bar, grad, u0_bar, u1, stream);
+}
+
+int cnf_vjp_path_for(const cnf_handle* h, int64_t B, int alg, int on_grid) {
+    (void)on_grid;
+    if (!h || B < 0 || (alg != CNF_ALG_RK4 && alg != CNF_ALG_TSIT5)) return CNF_ERR_INVALID;
+    return vjp_route(h);
+}
+
+}  // extern "C"

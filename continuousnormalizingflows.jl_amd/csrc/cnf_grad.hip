@@ -126,9 +126,12 @@ void grad_shape(const cnf_config& c, int* HT, int* L, int* ZR, int* CR) {
 hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float* ckpt, const float* ckpt_k,
                        int ckpt_zr, const float* eps, const float* ys,
                        const size_t* w_off, const size_t* b_off, int alg, int nsteps, float t0, float t1, const float* tgrid_dev,
-                       float probe_w, long long B, const float lam[3], float* slab, float* grad, float* grad_x, int num_cus, hipStream_t st) {
+                       float probe_w, long long B, const float lam[3], float* slab, float* grad, float* grad_x, int num_cus, hipStream_t st,
+                       const float* u1_bar, float* u0_bar) {
     const GradInst* gi = grad_find(c);
     if (!gi) return hipErrorNotSupported;
+    const bool cot = u1_bar != nullptr;   // the pullback of the solve (cnf_grad2_cot.hip): one probe only
+    if (cot && c.nprobes != 1) return hipErrorNotSupported;
     // > 64 KB of dynamic LDS has to be enabled once per device and kernel
     const int idx = (int)(gi - kGrad);
     int dev = 0;
@@ -136,12 +139,13 @@ hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float
     if (e0 != hipSuccess) return e0;
     // one probe / several probes (the probe loop rolled around the pullback and its bottom-up reverse): cnf_grad2.hip compiled twice
     if (!ckpt_k) return hipErrorNotSupported;   // the sweep reads the forward kernel's stage checkpoints
-    const GradKernel kern = c.nprobes == 1 ? grad2_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : grad2_probes_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT);
-    if (!kern) return hipErrorNotSupported;
-    static DeviceOnce done_one[sizeof(kGrad) / sizeof(kGrad[0])], done_probes[sizeof(kGrad) / sizeof(kGrad[0])];
-    DeviceOnce& done = (c.nprobes > 1 ? done_probes : done_one)[idx];
+    const GradCotKernel kern_cot = cot ? grad2_cot_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : nullptr;
+    const GradKernel kern = cot ? nullptr : c.nprobes == 1 ? grad2_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : grad2_probes_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT);
+    if (!kern && !kern_cot) return hipErrorNotSupported;
+    static DeviceOnce done_one[sizeof(kGrad) / sizeof(kGrad[0])], done_probes[sizeof(kGrad) / sizeof(kGrad[0])], done_cot[sizeof(kGrad) / sizeof(kGrad[0])];
+    DeviceOnce& done = (cot ? done_cot : c.nprobes > 1 ? done_probes : done_one)[idx];
     if (!done.done(dev)) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, gi->lds_bytes);
+        hipError_t e = hipFuncSetAttribute(cot ? (const void*)kern_cot : (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, gi->lds_bytes);
         if (e != hipSuccess) return e;
         done.set(dev);
     }
@@ -158,7 +162,14 @@ hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float
     const int nwaves = nblocks * 4;
     hipError_t e = zero_async(slab, (size_t)nwaves * gi->slab_total * sizeof(float), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), gi->lds_bytes, st, a);
+    if (cot) {
+        GArgsCot ac{};
+        static_cast<GArgs&>(ac) = a;
+        ac.u1_bar = u1_bar; ac.u0_bar = u0_bar;
+        hipLaunchKernelGGL(kern_cot, dim3(nblocks), dim3(256), gi->lds_bytes, st, ac);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), gi->lds_bytes, st, a);
+    }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gi->reduce, dim3((gi->slab_total + 63) / 64), dim3(1024), 0, st, slab, nwaves, a, grad);

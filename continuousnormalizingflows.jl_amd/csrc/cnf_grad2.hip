@@ -23,10 +23,15 @@
 #include "cnf_grad_dev.h"
 #include "cnf_sched_dev.h"
 
-// compiled twice: cnf_grad2.hip (one probe) and cnf_grad2_probes.hip (-DG2_MULTI=true: several probes)
+// compiled three times: cnf_grad2.hip (one probe), cnf_grad2_probes.hip (-DG2_MULTI=true: several probes) and cnf_grad2_cot.hip
+// (-DG2_COT=true: one probe, the terminal costate and the row cotangents from the caller)
 #ifndef G2_FIND
 #define G2_FIND grad2_kernel
 #endif
+#ifndef G2_COT
+#define G2_COT false
+#endif
+#include <type_traits>
 
 #ifdef G2_TRACE
 #define G2_T(k) do { asm volatile("" ::: "memory"); tr[k] = __builtin_amdgcn_s_memtime(); asm volatile("" ::: "memory"); } while (0)
@@ -167,9 +172,12 @@ __device__ __forceinline__ StageCoef stage_coef(const float* tab, int st) {   //
 // MULTI: several Hutchinson probes (a.K of them; the probes share the forward chain and the top-down
 // pass, the pullback and its bottom-up reverse run once per probe and a2_l = sum_k dbar_l^k .* u_l^k).  The probe loop is rolled:
 // eps_k is read from global memory one probe ahead, c_k = W_N^T eps_k is multiplied per probe (HT x ZR MFMAs of ~450 per probe).
-template <int HT, int L, int ZR, int CR, int ACT, bool MULTI>
+// COT: the pullback of the solve instead of the gradient of the shipped loss - the terminal costate is rows 0 .. D-1 of the caller's
+// u1_bar (no z_N, no l3 term), the cotangents of ldot / Edot / ndot are dt b_i times rows D .. D+2 of the lane's sample (three more
+// per-lane floats), and the costate at t0 goes to u0_bar with those three rows passed through.  Everything between is unchanged.
+template <int HT, int L, int ZR, int CR, int ACT, bool MULTI, bool COT>
 __global__ void __launch_bounds__(256)
-mfma_grad2_kernel(GArgs a) {
+mfma_grad2_kernel(std::conditional_t<COT, GArgsCot, GArgs> a) {
     using G = GradLds<HT, L, ZR, CR, ACT>;
     using SL = GradSlab<HT, L, ZR, CR>;
     constexpr MfmaLayout LAY(HT, L, ZR, CR, true, 0);
@@ -224,14 +232,20 @@ mfma_grad2_kernel(GArgs a) {
         const bool valid = smp < a.B;
         const long long sc = valid ? smp : a.B - 1;
         float eps[ZR], lam[ZR];
+        float ub[3] = {0.f, 0.f, 0.f};   // cotangent form: u1_bar's rows D .. D+2 of the lane's sample (zero for padding columns)
 #pragma unroll
         for (int s = 0; s < ZR; ++s) {
             const int f = 4 * s + g;
             eps[s] = f < D ? a.eps[sc * K * D + f] : 0.f;   // probe 0
             // dL/dz_N = z_N  (L = sum_j -logp_j, -log N(z) = |z|^2/2 + const); zero for padding columns
-            lam[s] = valid ? a.ckpt[(((long long)a.nsteps * ntiles + tile) * 64 + lane) * a.ckpt_zr + s] : 0.f;
+            if constexpr (COT) lam[s] = (valid && f < D) ? a.u1_bar[sc * (D + 3) + f] : 0.f;
+            else lam[s] = valid ? a.ckpt[(((long long)a.nsteps * ntiles + tile) * 64 + lane) * a.ckpt_zr + s] : 0.f;
         }
-        if (a.lam3 != 0.f) {   // + l3 |z_aug|_2 at the final time (src/core/base_icnf.jl:106-122)
+        if constexpr (COT) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) ub[r] = valid ? a.u1_bar[sc * (D + 3) + D + r] : 0.f;
+        }
+        if (!COT && a.lam3 != 0.f) {   // + l3 |z_aug|_2 at the final time (src/core/base_icnf.jl:106-122)
             float sa = 0.f;
 #pragma unroll
             for (int s = 0; s < ZR; ++s) { const int f = 4 * s + g; if (f >= a.nvars && f < D) sa = fmaf(lam[s], lam[s], sa); }
@@ -313,8 +327,8 @@ mfma_grad2_kernel(GArgs a) {
                     zs[s] = fmaf(dt, acc, zn[s]);
                     kbar[s] = dt * kb;
                 }
-                const float cl = valid ? dt * bi : 0.f;   // cotangent of ldot: dL/d(dlogp) = +1
-                const float cE = cl * a.lam1, cn = cl * a.lam2;   // cotangents of Edot, ndot
+                const float cl = COT ? dt * bi * ub[0] : (valid ? dt * bi : 0.f);   // cotangent of ldot: dL/d(dlogp) = +1
+                const float cE = COT ? dt * bi * ub[1] : cl * a.lam1, cn = COT ? dt * bi * ub[2] : cl * a.lam2;   // cotangents of Edot, ndot
                 const bool regz = a.lam1 != 0.f, regj = a.lam2 != 0.f;   // wave-uniform
                 const float tt = tn + sc_cur.c * dt;
                 int opaque = 0;
@@ -680,7 +694,19 @@ mfma_grad2_kernel(GArgs a) {
                 for (int j = 0; j < 6; ++j) kz[j][s] = kz_nx[j][s];
             }
         }
-        if (a.grad_x && valid) {   // costate at t0 = dL/dz_0; its first nvars rows are dL/dx
+        if constexpr (COT) {
+            if (a.u0_bar && valid) {   // the costate at t0 is the cotangent of z_0; rows D .. D+2 feed nothing: passed through
+#pragma unroll
+                for (int s = 0; s < ZR; ++s) {
+                    const int f = 4 * s + g;
+                    if (f < D) a.u0_bar[smp * (D + 3) + f] = lam[s];
+                }
+                if (g == 0) {
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) a.u0_bar[smp * (D + 3) + D + r] = ub[r];
+                }
+            }
+        } else if (a.grad_x && valid) {   // costate at t0 = dL/dz_0; its first nvars rows are dL/dx
 #pragma unroll
             for (int s = 0; s < ZR; ++s) {
                 const int f = 4 * s + g;
@@ -721,14 +747,15 @@ mfma_grad2_kernel(GArgs a) {
 // ---------------------------------------------------------------------------------------
 // host side: instance table (the launch itself is grad_launch's, cnf_grad.hip)
 // ---------------------------------------------------------------------------------------
+typedef std::conditional_t<G2_COT, GradCotKernel, GradKernel> G2Kernel;
 struct Grad2Inst {
     int HT, L, ZR, CR, ACT;
-    GradKernel kern;
+    G2Kernel kern;
 };
 #ifndef G2_MULTI
 #define G2_MULTI false
 #endif
-#define G2_INST(HT, L, ZR, CR, ACT) Grad2Inst { HT, L, ZR, CR, ACT, &mfma_grad2_kernel<HT, L, ZR, CR, ACT, G2_MULTI> }
+#define G2_INST(HT, L, ZR, CR, ACT) Grad2Inst { HT, L, ZR, CR, ACT, &mfma_grad2_kernel<HT, L, ZR, CR, ACT, G2_MULTI, G2_COT> }
 // the shapes of cnf_grad.hip's table (kGrad): 1 .. 4 hidden tiles, 2 / 3 hidden layers, D <= 8 / 16, with and without conditions
 #define G2_HT(HT, CR, ACT) G2_INST(HT, 3, 2, CR, ACT), G2_INST(HT, 2, 2, CR, ACT), G2_INST(HT, 3, 4, CR, ACT), G2_INST(HT, 2, 4, CR, ACT)
 #define G2_SHAPES(CR, ACT) G2_HT(1, CR, ACT), G2_HT(2, CR, ACT), G2_HT(3, CR, ACT), G2_HT(4, CR, ACT)
@@ -738,7 +765,7 @@ static const Grad2Inst kGrad2[] = {G2_ONLY};
 static const Grad2Inst kGrad2[] = {G2_SHAPES(0, CNF_ACT_TANH), G2_SHAPES(0, CNF_ACT_SOFTPLUS), G2_SHAPES(4, CNF_ACT_TANH), G2_SHAPES(4, CNF_ACT_SOFTPLUS)};
 #endif
 
-GradKernel G2_FIND(int HT, int L, int ZR, int CR, int ACT) {
+G2Kernel G2_FIND(int HT, int L, int ZR, int CR, int ACT) {
     for (const Grad2Inst& g : kGrad2)
         if (g.HT == HT && g.L == L && g.ZR == ZR && g.CR == CR && g.ACT == ACT) return g.kern;
     return nullptr;

@@ -27,6 +27,14 @@ struct GArgs {
     int w_off[4], b_off[4];   // Lux offsets of the L+1 <= 4 Dense layers
     Tableau T;
 };
+// The argument block of the cotangent form (cnf_grad2_cot.hip: the pullback of the solve, cnf_integrate_*_vjp) - GArgs itself is
+// left as it is, so the kernels that take it are compiled from the same argument layout as before.  u1_bar: the caller's cotangent of
+// the final state; u0_bar: where the cotangent of the initial state goes; both S x B with S = D + 3.  There lam1 / lam2 are the
+// handle's reg_z / reg_j as 0 / 1 switches (the weights are rows D + 1, D + 2 of u1_bar), lam3 is unused and grad_x is null.
+struct GArgsCot : GArgs {
+    const float* u1_bar;
+    float* u0_bar;         // or null
+};
 
 // Cross-wave exchange of accumulator-layout tiles through LDS.  A tile is stored with 8 dwords of
 // padding per 16-lane group (TS = 280 floats), which makes both transposed fragment reads below
@@ -137,5 +145,7 @@ __device__ __forceinline__ void grad_forward(const float* __restrict__ smem, int
 typedef void (*GradKernel)(GArgs);
 GradKernel grad2_kernel(int HT, int L, int ZR, int CR, int ACT);
 GradKernel grad2_probes_kernel(int HT, int L, int ZR, int CR, int ACT);   // the same for several probes (cnf_grad2_probes.hip)
+typedef void (*GradCotKernel)(GArgsCot);
+GradCotKernel grad2_cot_kernel(int HT, int L, int ZR, int CR, int ACT);   // one probe, cotangent form (cnf_grad2_cot.hip)
 
 }  // namespace cnf

@@ -115,9 +115,16 @@ void grad_pack(const cnf_config& c, const float* lux, const size_t* w_off, const
 hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float* ckpt, const float* ckpt_k,
                        int ckpt_zr, const float* eps, const float* ys,
                        const size_t* w_off, const size_t* b_off, int alg, int nsteps, float t0, float t1, const float* tgrid_dev,
-                       float probe_w, long long B, const float lam[3], float* slab, float* grad, float* grad_x, int num_cus, hipStream_t st);
+                       float probe_w, long long B, const float lam[3], float* slab, float* grad, float* grad_x, int num_cus, hipStream_t st,
+                       const float* u1_bar = nullptr, float* u0_bar = nullptr);
+// u1_bar (S x B): the cotangent form - the pullback of the solve whose checkpoints are given (one probe; lam[0] / lam[1] are then the
+// 0 / 1 switches of the E / n rows, lam[2] and grad_x unused); u0_bar (S x B or null) receives the cotangent of the initial state
 // layer-wise evaluation / gradient on the product kernels of cnf_lgemm.hip for everything the fused kernels do not cover (cnf_layered.hip)
 struct LayeredGrad;
+// the cotangent form of layered_grad (the pullback of the solve, cnf_integrate_*_vjp): the solve starts from u0 (S x B, all rows),
+// the terminal costate and the per-column cotangents of the dlogp / E / n rows come from u1_bar (S x B); u0_bar / u1 (S x B) or null.
+// x, lam[2], grad_x, logp_out and regs_out are then unused; lam[0] / lam[1] are the 0 / 1 switches of the E / n rows.
+struct LayeredCot { const float* u0; const float* u1_bar; float* u0_bar; float* u1; };
 bool layered_available();   // always: the products are the library's own kernels (cnf_lgemm.hip)
 bool layered_supports(const cnf_config& c);   // every layer within the product kernels' limits (512 outputs, 639 inputs)
 hipError_t layered_aug_f(LayeredGrad** ctx, const cnf_config& c, const float* P_dev, const size_t* w_off,
@@ -128,7 +135,8 @@ void layered_grad_destroy(LayeredGrad* g);
 hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_dev, const size_t* w_off,
                         const size_t* b_off, const float* x, const float* eps, const float* ys, int alg,
                         int nsteps, float t0, float t1, const float* tgrid, long long B, const float lam[3], float* grad,
-                        float* grad_x, hipStream_t st, std::string* err, float* logp_out = nullptr, float* regs_out = nullptr);
+                        float* grad_x, hipStream_t st, std::string* err, float* logp_out = nullptr, float* regs_out = nullptr,
+                        const LayeredCot* cot = nullptr);
 // logp_out (B) / regs_out (3 B): when both are given the reverse sweep also accumulates the loss terms of the same discrete
 // solve (dlogp, E, n per column) and runs the epilogue - no separate forward solve for the loss
 void mfma_pack_layout(const cnf_config& c, int HT, int L, int ZR, int CR, const float* lux, const size_t* w_off,

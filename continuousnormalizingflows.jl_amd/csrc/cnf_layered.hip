@@ -163,8 +163,10 @@ __global__ void mul_kernel(float* __restrict__ out, const float* __restrict__ x,
 }
 
 // kbar = dt (b lam + sum_j a_j Zb_j)  (+ cE zdot / |zdot|: Edot = |zdot|, src/core/icnf.jl:184-199)
+// cw (null: the shipped loss, whose row cotangents are the uniform scalars): per-column cotangents of the dlogp / E / n rows, column j
+// at cw[j ldw + 0..2] (the pullback of the solve) - cE, and cl / cn in the gbar kernels, are then multiplied by the column's entry
 __global__ void kbar_kernel(float* __restrict__ kbar, const float* __restrict__ lam, Comb zb, float dtb, float dt,
-                            const float* __restrict__ aN, float cE, int D, long long B) {
+                            const float* __restrict__ aN, float cE, int D, long long B, const float* __restrict__ cw = nullptr, int ldw = 0) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= B) return;
     float inv = 0.f;
@@ -172,6 +174,7 @@ __global__ void kbar_kernel(float* __restrict__ kbar, const float* __restrict__ 
         float e2 = 0.f;
         for (int f = 0; f < D; ++f) { const float v = aN[j * (D + 1) + f]; e2 = fmaf(v, v, e2); }
         inv = e2 > 0.f ? cE * rsqrtf(e2) : 0.f;
+        if (cw) inv *= cw[j * ldw + 1];
     }
     for (int f = 0; f < D; ++f) {
         float acc = 0.f;
@@ -184,7 +187,7 @@ __global__ void kbar_kernel(float* __restrict__ kbar, const float* __restrict__ 
 
 // gbar = -c_l eps_k + c_n g / |g|   (cotangent of g = eps^T J; ldot = -<eps, g>/K, ndot = |g|/K)
 __global__ void gbar_kernel(float* __restrict__ gbar, const float* __restrict__ g, const float* __restrict__ epsk,
-                            float cl, float cn, int D, long long B) {
+                            float cl, float cn, int D, long long B, const float* __restrict__ cw = nullptr, int ldw = 0) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= B) return;
     float inv = 0.f;
@@ -193,6 +196,7 @@ __global__ void gbar_kernel(float* __restrict__ gbar, const float* __restrict__ 
         for (int f = 0; f < D; ++f) { const float v = g[j * D + f]; n2 = fmaf(v, v, n2); }
         inv = n2 > 0.f ? cn * rsqrtf(n2) : 0.f;
     }
+    if (cw) { cl *= cw[j * ldw]; inv *= cw[j * ldw + 2]; }
     for (int f = 0; f < D; ++f) gbar[j * D + f] = fmaf(inv, g[j * D + f], -cl * epsk[j * D + f]);
 }
 
@@ -232,7 +236,7 @@ __device__ __forceinline__ float group_sum_w(float v, int G) {
     return v;
 }
 __global__ void kbar_grp_kernel(float* __restrict__ kbar, const float* __restrict__ lam, Comb zb, float dtb, float dt,
-                                const float* __restrict__ aN, float cE, int D, int G, long long B) {
+                                const float* __restrict__ aN, float cE, int D, int G, long long B, const float* __restrict__ cw = nullptr, int ldw = 0) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long j = i / G;
     const int f = (int)(i % G);
@@ -242,6 +246,7 @@ __global__ void kbar_grp_kernel(float* __restrict__ kbar, const float* __restric
     if (cE != 0.f) {
         const float e2 = group_sum_w(z * z, G);
         inv = e2 > 0.f ? cE * rsqrtf(e2) : 0.f;
+        if (cw && ok) inv *= cw[j * ldw + 1];
     }
     if (!ok) return;
     float acc = 0.f;
@@ -252,7 +257,7 @@ __global__ void kbar_grp_kernel(float* __restrict__ kbar, const float* __restric
 }
 __global__ void gbar_grp_kernel(float* __restrict__ gbar, const float* __restrict__ g, const float* __restrict__ epsk,
                                 float cl, float cn, float* __restrict__ lacc, float* __restrict__ nacc, float wl, float wn,
-                                int D, int G, long long B) {
+                                int D, int G, long long B, const float* __restrict__ cw = nullptr, int ldw = 0) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long j = i / G;
     const int f = (int)(i % G);
@@ -268,6 +273,7 @@ __global__ void gbar_grp_kernel(float* __restrict__ gbar, const float* __restric
             if (wn != 0.f) nacc[j] = fmaf(wn, sqrtf(n2), nacc[j]);
         }
     }
+    if (cw && ok) { cl *= cw[j * ldw]; inv *= cw[j * ldw + 2]; }
     if (ok) gbar[j * D + f] = fmaf(inv, gv, -cl * ev);
 }
 __global__ void loss_acc_z_grp_kernel(float* __restrict__ eacc, const float* __restrict__ aN, int ldn, float w, int D, int G, long long B) {
@@ -319,6 +325,23 @@ __global__ void lam_init_kernel(float* __restrict__ lam, const float* __restrict
     }
 }
 
+// the pullback of the solve: the dlogp / E / n accumulators start from rows D .. D+2 of u0 (S x B), not from zero
+__global__ void cot_rows_init_kernel(float* __restrict__ lacc, float* __restrict__ eacc, float* __restrict__ nacc,
+                                     const float* __restrict__ u0, int D, long long B) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B) return;
+    const int S = D + 3;
+    lacc[j] = u0[j * S + D]; eacc[j] = u0[j * S + D + 1]; nacc[j] = u0[j * S + D + 2];
+}
+// u0_bar = [costate at t0; rows D .. D+2 of u1_bar] (those rows feed nothing: passed through)
+__global__ void cot_out_kernel(float* __restrict__ u0_bar, const float* __restrict__ lam, const float* __restrict__ u1_bar, int D, long long B) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int S = D + 3;
+    if (i >= (long long)S * B) return;
+    const long long j = i / S;
+    const int f = (int)(i % S);
+    u0_bar[i] = f < D ? lam[j * D + f] : u1_bar[i];
+}
 
 // ---- forward evaluation (layered_aug_f) ----
 
@@ -682,7 +705,7 @@ hipError_t layered_aug_f(LayeredGrad** ctx, const cnf_config& c, const float* P_
 hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_dev, const size_t* w_off,
                         const size_t* b_off, const float* x, const float* eps, const float* ys, int alg,
                         int nsteps, float t0, float t1, const float* tgrid, long long B, const float lam[3], float* grad,
-                        float* grad_x, hipStream_t st, std::string* err, float* logp_out, float* regs_out) {
+                        float* grad_x, hipStream_t st, std::string* err, float* logp_out, float* regs_out, const LayeredCot* cot) {
     if (!layered_supports(c)) {
         *err = "layered gradient: a layer is wider than the product kernels cover (512 outputs, 639 inputs)";
         return hipErrorNotSupported;
@@ -826,7 +849,10 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
 
     // ---- forward sweep: checkpoints z_n ----
     float* zck = W + o_zck;
-    hipLaunchKernelGGL(init_state_kernel, grid_for(DB), dim3(TPB), 0, st, x, zck, c.nvars, D, B);
+    const float* cw = cot ? cot->u1_bar + D : nullptr;   // per-column cotangents of the dlogp / E / n rows (null: the shipped loss)
+    const int ldw = D + 3;
+    if (cot) hipLaunchKernelGGL(copy_rows_kernel, grid_for(DB), dim3(TPB), 0, st, zck, cot->u0, D, D + 3, 0, B);
+    else hipLaunchKernelGGL(init_state_kernel, grid_for(DB), dim3(TPB), 0, st, x, zck, c.nvars, D, B);
     float* kck = W + o_kck;
     for (int n = 0; n < nsteps; ++n) {
         dt = step_dt(n);
@@ -840,14 +866,17 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
         for (int j = 0; j < ns; ++j) { cb.k[j] = kz[j]; cb.coef[j] = dt * T.b[j]; }
         hipLaunchKernelGGL(combine_kernel, grid_for(DB), dim3(TPB), 0, st, zck + (long long)(n + 1) * DB, zck + (long long)n * DB, cb, DB);
     }
-    hipLaunchKernelGGL(lam_init_kernel, grid_for(B), dim3(TPB), 0, st, lamv, zck + (long long)nsteps * DB, lam[2], c.nvars, D, B);
+    if (cot) hipLaunchKernelGGL(copy_rows_kernel, grid_for(DB), dim3(TPB), 0, st, lamv, cot->u1_bar, D, D + 3, 0, B);
+    else hipLaunchKernelGGL(lam_init_kernel, grid_for(B), dim3(TPB), 0, st, lamv, zck + (long long)nsteps * DB, lam[2], c.nvars, D, B);
 
     // ---- reverse sweep ----
     const float invK = exact ? 1.f : 1.f / (float)K;
     // the loss of this solve is accumulated on the way (no separate forward solve for it): per column dlogp, E, n
-    const bool want_loss = logp_out != nullptr && regs_out != nullptr;
+    // (the pullback of the solve: the same accumulators, started from u0's rows, are the dlogp / E / n rows of u1)
+    const bool want_loss = cot ? cot->u1 != nullptr : (logp_out != nullptr && regs_out != nullptr);
     float *lacc = W + o_lacc, *eacc = lacc + B, *nacc = eacc + B;
-    if (want_loss) LG_HIP(zero_async(lacc, 3 * (size_t)B * sizeof(float), st));
+    if (want_loss && cot) hipLaunchKernelGGL(cot_rows_init_kernel, grid_for(B), dim3(TPB), 0, st, lacc, eacc, nacc, cot->u0, D, B);
+    else if (want_loss) LG_HIP(zero_async(lacc, 3 * (size_t)B * sizeof(float), st));
     const bool hutch = !exact;
     int Gw = 1;                      // lanes per column of the grouped per-column kernels (0: D > 64, thread-per-column forms)
     while (Gw < D) Gw <<= 1;
@@ -874,8 +903,8 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
             zb.nk = 0;
             for (int j = i + 1; j < ns; ++j)
                 if (T.a[j][i] != 0.f) { zb.k[zb.nk] = Zb[j]; zb.coef[zb.nk] = T.a[j][i]; ++zb.nk; }
-            if (Gw) hipLaunchKernelGGL(kbar_grp_kernel, grid_for(B * Gw), dim3(TPB), 0, st, kbar, lamv, zb, dt * T.b[i], dt, a[N], cl * lam[0], D, Gw, B);
-            else hipLaunchKernelGGL(kbar_kernel, grid_for(B), dim3(TPB), 0, st, kbar, lamv, zb, dt * T.b[i], dt, a[N], cl * lam[0], D, B);
+            if (Gw) hipLaunchKernelGGL(kbar_grp_kernel, grid_for(B * Gw), dim3(TPB), 0, st, kbar, lamv, zb, dt * T.b[i], dt, a[N], cl * lam[0], D, Gw, B, cw, ldw);
+            else hipLaunchKernelGGL(kbar_kernel, grid_for(B), dim3(TPB), 0, st, kbar, lamv, zb, dt * T.b[i], dt, a[N], cl * lam[0], D, B, cw, ldw);
             if (want_loss && hutch && c.reg_z) {
                 if (Gw) hipLaunchKernelGGL(loss_acc_z_grp_kernel, grid_for(B * Gw), dim3(TPB), 0, st, eacc, a[N], D + 1, cl, D, Gw, B);
                 else hipLaunchKernelGGL(loss_acc_z_kernel, grid_for(B), dim3(TPB), 0, st, eacc, a[N], D + 1, cl, D, B);
@@ -896,9 +925,9 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
                     }
                     if (Gw) {
                         hipLaunchKernelGGL(gbar_grp_kernel, grid_for(B * Gw), dim3(TPB), 0, st, gbar, dl[N - 1], vN, cl * invK, cl * lam[1] * invK,
-                                           want_loss ? lacc : nullptr, nacc, -cl * invK, c.reg_j ? cl * invK : 0.f, D, Gw, B);
+                                           want_loss ? lacc : nullptr, nacc, -cl * invK, c.reg_j ? cl * invK : 0.f, D, Gw, B, cw, ldw);
                     } else {
-                        hipLaunchKernelGGL(gbar_kernel, grid_for(B), dim3(TPB), 0, st, gbar, dl[N - 1], vN, cl * invK, cl * lam[1] * invK, D, B);
+                        hipLaunchKernelGGL(gbar_kernel, grid_for(B), dim3(TPB), 0, st, gbar, dl[N - 1], vN, cl * invK, cl * lam[1] * invK, D, B, cw, ldw);
                         if (want_loss)
                             hipLaunchKernelGGL(loss_acc_g_kernel, grid_for(B), dim3(TPB), 0, st, lacc, nacc, dl[N - 1], vN, -cl * invK,
                                                c.reg_j ? cl * invK : 0.f, D, B);
@@ -928,9 +957,9 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
                 LG_BLAS(gemm(OPT, OPN, D, B, L.wout[0], PA, L.wout[0], dl[0], L.wout[0], gk, D));
                 if (Gw) {
                     hipLaunchKernelGGL(gbar_grp_kernel, grid_for(B * Gw), dim3(TPB), 0, st, gbar, gk, vN, cl * invK, cl * lam[1] * invK,
-                                       want_loss ? lacc : nullptr, nacc, -cl * invK, (hutch && c.reg_j) ? cl * invK : 0.f, D, Gw, B);
+                                       want_loss ? lacc : nullptr, nacc, -cl * invK, (hutch && c.reg_j) ? cl * invK : 0.f, D, Gw, B, cw, ldw);
                 } else {
-                    hipLaunchKernelGGL(gbar_kernel, grid_for(B), dim3(TPB), 0, st, gbar, gk, vN, cl * invK, cl * lam[1] * invK, D, B);
+                    hipLaunchKernelGGL(gbar_kernel, grid_for(B), dim3(TPB), 0, st, gbar, gk, vN, cl * invK, cl * lam[1] * invK, D, B, cw, ldw);
                     if (want_loss)
                         hipLaunchKernelGGL(loss_acc_g_kernel, grid_for(B), dim3(TPB), 0, st, lacc, nacc, gk, vN, -cl * invK,
                                            (hutch && c.reg_j) ? cl * invK : 0.f, D, B);
@@ -973,6 +1002,12 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
         hipLaunchKernelGGL(combine_kernel, grid_for(DB), dim3(TPB), 0, st, lamv, lamv, cb, DB);
     }
     hipLaunchKernelGGL(reduce_slabs_kernel, grid_for(npa), dim3(TPB), 0, st, slabs, nslab, npa_pad, L, grad);
+    if (cot) {
+        if (cot->u0_bar) hipLaunchKernelGGL(cot_out_kernel, grid_for((long long)(D + 3) * B), dim3(TPB), 0, st, cot->u0_bar, lamv, cot->u1_bar, D, B);
+        if (cot->u1) hipLaunchKernelGGL(pack_final_kernel, grid_for(B), dim3(TPB), 0, st, cot->u1, zck + (long long)nsteps * DB, lacc, eacc, nacc, D, B);
+        LG_HIP(hipGetLastError());
+        return hipSuccess;
+    }
     if (grad_x)   // costate at t0: dL/dx = its first nvars rows
         hipLaunchKernelGGL(copy_rows_kernel, grid_for((long long)c.nvars * B), dim3(TPB), 0, st, grad_x, lamv, c.nvars, D, 0, B);
     if (want_loss) {   // inference_sol on [z(t1); dlogp; E; n] (src/core/base_icnf.jl:158-172)

@@ -35,7 +35,7 @@ __all__ = [
     "sigmoid", "swish", "elu", "gelu",
     "HIPVecJacMatrixMode", "HIPJacVecMatrixMode", "LuxVecJacMatrixMode", "LuxJacVecMatrixMode",
     "DIVecJacMatrixMode", "DIJacVecMatrixMode", "Tsit5", "RK4", "VCABM", "setup", "inference", "generate",
-    "loss", "augmented_f", "loss_and_gradient",
+    "loss", "augmented_f", "loss_and_gradient", "integrate_vjp", "vjp_path",
 ]
 
 
@@ -597,8 +597,170 @@ def _split_args(icnf: ICNF, args, what: str):
     return args[0], None, args[1], args[2]
 
 
+# ---------------------------------------------------------------------------------------
+# the solve as an autograd node (cnf_integrate_fixed_vjp / cnf_integrate_grid_vjp)
+# ---------------------------------------------------------------------------------------
+def vjp_path(icnf: ICNF, mode: Mode, B: int, alg: int = _lib.ALG_TSIT5, on_grid: bool = False) -> int:
+    """Which implementation the pullback of the solve takes for this mode's handle (cnf_vjp_path_for): 1 the fused per-wave
+    sweep in its cotangent form, 2 the layer-wise sweep, 0 none."""
+    h = icnf._handle(mode)
+    return int(h.lib.cnf_vjp_path_for(h.ptr, int(B), int(alg), int(on_grid)))
+
+
+def _vjp_call(icnf: ICNF, h: _Handle, ps: torch.Tensor, u0c, e, y, alg: int, t0: float, t1: float, nsteps: int, tgrid, u1_bar_c,
+              want_u0_bar: bool = True, want_u1: bool = False):
+    """One library call on column-major (B, S) tensors: (gradient in ps's own layout, u0_bar or None, u1 or None)."""
+    dev = icnf.device
+    B = u0c.shape[0]
+    n_abi = ps.numel() if icnf.nn.planar is None else icnf.nn.abi_params(ps).numel()
+    grad = torch.empty(n_abi, device=dev, dtype=torch.float32)
+    u0_bar = torch.empty_like(u0c) if want_u0_bar else None
+    u1 = torch.empty_like(u0c) if want_u1 else None
+    sp = _stream_ptr(dev)
+    if tgrid is not None:
+        grid = (C.c_float * len(tgrid))(*tgrid)
+        _lib.check(h.lib.cnf_integrate_grid_vjp(h.ptr, alg, len(tgrid) - 1, grid, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1_bar_c),
+                                                _ptr(grad), _ptr(u0_bar), _ptr(u1), sp))
+    else:
+        _lib.check(h.lib.cnf_integrate_fixed_vjp(h.ptr, alg, nsteps, t0, t1, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1_bar_c),
+                                                 _ptr(grad), _ptr(u0_bar), _ptr(u1), sp))
+    return grad[:ps.numel()], u0_bar, u1
+
+
+def integrate_vjp(icnf: ICNF, mode: Mode, u0: torch.Tensor, ps: torch.Tensor, u1_bar: torch.Tensor, *, t0: float, t1: float,
+                  eps: Optional[torch.Tensor], ys: Optional[torch.Tensor] = None, tgrid: Optional[Sequence[float]] = None):
+    """The pullback of the fixed-step solve u1 = integrate(u0; ps) - what the reference's ZygoteVJP pullback of `solve` returns
+    (src/core/icnf.jl:90-99): for a cotangent `u1_bar` ((S, B)) of the final state, `(grad_ps, u0_bar, u1)` with
+    `grad_ps = u1_bar^T du1/dps`, `u0_bar = u1_bar^T du1/du0` ((S, B)) and the forward result `u1`.  The steps are those of
+    `sol_kwargs` (`nsteps`, or `dt` with the tail step of the fixed-dt plan) from t0 to t1 - t1 < t0 integrates backwards as
+    `generate` does - or the times of `tgrid`.  `eps` ((K*D, B)) are the Hutchinson probes of the solve (ignored in TestMode).
+    A shard's `grad_ps` is the partial sum over its columns."""
+    if icnf._solver() == _lib.ALG_VCABM:
+        raise NotImplementedError("integrate_vjp: VCABM has no one-step discrete adjoint; use Tsit5 or RK4 (the pullback of a "
+                                  "frozen adaptive grid is the `tgrid` argument)")
+    h = icnf._handle(mode)
+    icnf._bind_params(h, ps)
+    dev = icnf.device
+    u0c = _colmajor(u0, icnf.S, "u0", dev)
+    ubc = _colmajor(u1_bar, icnf.S, "u1_bar", dev)
+    B = u0c.shape[0]
+    if ubc.shape[0] != B:
+        raise ValueError("DimensionMismatch: u0 and u1_bar must have the same number of columns")
+    K = icnf.nprobes if isinstance(mode, TrainMode) else 1
+    e = None if eps is None else _colmajor(eps, K * icnf.D, "eps", dev)
+    y = _colmajor(ys, icnf.nconditions, "ys", dev) if icnf.conditioned else None
+    grid, nsteps = _fixed_plan(icnf, t0, t1) if tgrid is None else ([float(t) for t in tgrid], 0)
+    g, u0_bar, u1 = _vjp_call(icnf, h, ps, u0c, e, y, icnf._solver(), t0, t1, nsteps, grid, ubc, True, True)
+    return g, u0_bar.t(), u1.t()
+
+
+def _fixed_plan(icnf: ICNF, t0: float, t1: float):
+    """(grid or None, nsteps) of a fixed-step solve from t0 to t1 under icnf.sol_kwargs, as loss_and_gradient plans it: equal
+    steps, or - fixed dt with a shorter last step - the grid of cnf_integrate_fixed_dt."""
+    dt = icnf._fixed_dt()
+    ts = icnf.fixed_dt_grid(t0, t1, dt) if dt is not None else None
+    if ts is not None and len(ts) >= 2 and abs(abs(ts[-1] - ts[-2]) - abs(ts[1] - ts[0])) > 1e-7 * abs(t1 - t0):
+        return ts, len(ts) - 1
+    return None, ((len(ts) - 1) if ts is not None and len(ts) >= 2 else icnf._nsteps(t0, t1))
+
+
+class _Solve(torch.autograd.Function):
+    """u1 = integrate(u0; ps) on column-major (B, S) states.  The forward is the library's plain solve; the backward is one
+    cnf_integrate_*_vjp call on the current stream, on the steps the forward took (an adaptive Tsit5 solve: its accepted steps,
+    frozen).  Nothing is kept in the library's handle between the two."""
+
+    @staticmethod
+    def forward(ctx, u0c, ps, icnf, mode, e, y, t0, t1, group):
+        h = icnf._handle(mode)
+        icnf._bind_params(h, ps)
+        dev = icnf.device
+        B = u0c.shape[0]
+        alg = icnf._solver()
+        u0c = u0c.contiguous()
+        if icnf.adaptive:
+            u1 = _adaptive_integrate(icnf, h, u0c, t0, t1, e, y, group=group, _tsit5=True)
+            ts = [t0]
+            for d in icnf.last_solve_stats["dts"]:
+                ts.append(ts[-1] + d)
+            ts[-1] = t1
+            icnf.last_solve_stats["tgrid"] = ts
+            grid, nsteps, alg = ts, len(ts) - 1, _lib.ALG_TSIT5
+        else:
+            grid, nsteps = _fixed_plan(icnf, t0, t1)
+            u1 = torch.empty_like(u0c)
+            dt = icnf._fixed_dt()
+            if dt is not None:
+                _lib.check(h.lib.cnf_integrate_fixed_dt(h.ptr, alg, dt, t0, t1, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1), _stream_ptr(dev)))
+            else:
+                _lib.check(h.lib.cnf_integrate_fixed(h.ptr, alg, nsteps, t0, t1, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1), _stream_ptr(dev)))
+        ctx.save_for_backward(u0c, ps)
+        ctx.rest = (icnf, mode, e, y, alg, t0, t1, nsteps, grid)
+        return u1
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, u1_bar):
+        u0c, ps = ctx.saved_tensors
+        icnf, mode, e, y, alg, t0, t1, nsteps, grid = ctx.rest
+        h = icnf._handle(mode)
+        icnf._bind_params(h, ps)
+        g, u0_bar, _ = _vjp_call(icnf, h, ps, u0c, e, y, alg, t0, t1, nsteps, grid, u1_bar.contiguous().to(torch.float32),
+                                 ctx.needs_input_grad[0], False)
+        return u0_bar, (g if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None
+
+
+def _check_differentiable(icnf: ICNF, ys, what: str):
+    if icnf._solver() == _lib.ALG_VCABM:
+        raise NotImplementedError(f"{what}(differentiable=True): VCABM has no one-step discrete adjoint here; use "
+                                  "sol_kwargs alg=Tsit5() (adaptive or fixed-step) or RK4(), or loss_and_gradient, which "
+                                  "differentiates the adaptive Tsit5 discretisation instead")
+    if ys is not None and getattr(ys, "requires_grad", False):
+        raise NotImplementedError(f"{what}(differentiable=True): no gradient with respect to ys; pass ys.detach() "
+                                  "(the conditions enter the solve as constants)")
+
+
+def _inference_differentiable(icnf: ICNF, mode: Mode, xs, ys, ps, eps, return_state: bool, group):
+    """inference with the solve as an autograd node and the epilogue in plain torch: logp, E, n, A (and the state) carry
+    gradients to ps and xs."""
+    _check_differentiable(icnf, ys, "inference")
+    dev = icnf.device
+    D, nv = icnf.D, icnf.nvariables
+    if xs.dim() != 2 or xs.shape[0] != nv:
+        raise ValueError(f"DimensionMismatch: xs must be ({nv}, B), got {tuple(xs.shape)}")
+    if xs.device != dev:
+        raise ValueError(f"xs must live on {dev} (got {xs.device})")
+    B = xs.shape[1]
+    y = _colmajor(ys, icnf.nconditions, "ys", dev) if icnf.conditioned else None
+    if y is not None and y.shape[0] != B:
+        raise ValueError("DimensionMismatch: xs and ys must have the same number of columns")
+    K = icnf.nprobes if isinstance(mode, TrainMode) else 1
+    if eps is None:
+        e = _draw_eps(icnf, K, B)     # drawn once per call; the backward reuses it
+    else:
+        e = _colmajor(eps, K * D, "eps", dev)
+        if e.shape[0] != B:
+            raise ValueError("DimensionMismatch: eps must have B columns")
+    t0, t1 = icnf._steer_tspan(mode)
+    u0c = torch.cat([xs.to(torch.float32).t(), torch.zeros(B, icnf.S - nv, device=dev, dtype=torch.float32)], dim=1)
+    uf = _Solve.apply(u0c, ps, icnf, mode, e, y, t0, t1, group)
+    z = uf[:, :D]
+    if icnf.basedist is not None:
+        logp = icnf.basedist.log_prob(z).to(torch.float32) - uf[:, D]
+    else:
+        logp = -0.5 * (z * z).sum(dim=1) - 0.5 * D * math.log(2.0 * math.pi) - uf[:, D]
+    reg = isinstance(mode, TrainMode) and mode.reg
+    if reg and icnf.lambda3 != 0.0 and icnf.augmented:   # A = |z_aug| (src/core/base_icnf.jl:106-122)
+        A = torch.sqrt((z[:, nv:] * z[:, nv:]).sum(dim=1))
+    else:
+        A = torch.zeros(B, device=dev, dtype=torch.float32)
+    out = (logp, (uf[:, D + 1], uf[:, D + 2], A))
+    if return_state:
+        return out + (uf.t(),)
+    return out
+
+
 def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
-              return_state: bool = False, _raw: bool = False, group=None, _sp=None):
+              return_state: bool = False, _raw: bool = False, group=None, _sp=None, differentiable: bool = False):
     """inference(icnf, mode, xs[, ys], ps, st) -> (logp̂x (B,), (Ė, ṅ, Ȧ)).
 
     `eps` ((K*D, B)) pins the Hutchinson probes; by default they are drawn from icnf.rng as
@@ -606,9 +768,17 @@ def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
     `group`: under an ADAPTIVE solver the error norm couples all columns, so when the batch is sharded over ranks the
     solve all-reduces its error sums over `group` (None = the default group / the installed Comm) and every rank must
     make this call; `group=False` (or `icnf.sharded = False`) runs a rank-local solve with no collectives.  Fixed-step
-    solves never communicate."""
+    solves never communicate.
+    `differentiable=True`: the solve is a torch.autograd node (its backward is the library's pullback of the solve,
+    cnf_integrate_*_vjp) and the epilogue - log N(z) or `icnf.basedist.log_prob(z)`, minus dlogp; A = |z_aug| - is plain torch,
+    so logp, E, n, A and the returned state carry gradients to `ps` and `xs`: any scalar built on them can be differentiated
+    (sample weights, another base distribution, a logsumexp over flows).  Under an adaptive Tsit5 solver the backward runs on
+    the steps the forward accepted.  Not with VCABM, and not with respect to `ys`.  Each rank's gradient is the partial sum
+    of its own columns."""
     xs, ys, ps, st = _split_args(icnf, args, "inference")
     group = icnf._group(group)
+    if differentiable:
+        return _inference_differentiable(icnf, mode, xs, ys, ps, eps, return_state, group)
     h = icnf._handle(mode)
     icnf._bind_params(h, ps)
     dev = icnf.device
@@ -658,9 +828,11 @@ def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
 
 
 def generate(icnf: ICNF, mode: Mode, *args, z0: Optional[torch.Tensor] = None,
-             eps: Optional[torch.Tensor] = None, group=None):
+             eps: Optional[torch.Tensor] = None, group=None, differentiable: bool = False):
     """generate(icnf, mode, [ys,] ps, st, n) -> (nvariables, n) samples: integrate the base
-    sample backwards over the reversed tspan (src/core/base_icnf.jl:351-404, 185-194)."""
+    sample backwards over the reversed tspan (src/core/base_icnf.jl:351-404, 185-194).
+    `differentiable=True`: the solve is a torch.autograd node (see `inference`), so the samples carry gradients to `ps` and to
+    `z0` - training on generated samples (reverse KL)."""
     if icnf.conditioned:
         if len(args) != 4:
             raise TypeError("MethodError: generate(icnf, mode, ys, ps, st, n) expected")
@@ -670,6 +842,8 @@ def generate(icnf: ICNF, mode: Mode, *args, z0: Optional[torch.Tensor] = None,
             raise TypeError("MethodError: generate(icnf, mode, ps, st, n) expected")
         ps, st, n = args
         ys = None
+    if differentiable:
+        _check_differentiable(icnf, ys, "generate")
     h = icnf._handle(mode)
     icnf._bind_params(h, ps)
     dev = icnf.device
@@ -687,6 +861,11 @@ def generate(icnf: ICNF, mode: Mode, *args, z0: Optional[torch.Tensor] = None,
     u0 = torch.zeros(n, S, device=dev, dtype=torch.float32)
     u0[:, :D] = z
     t0, t1 = icnf._steer_tspan(mode)
+    if differentiable:
+        if z.requires_grad:   # (z0 given with a graph: the state is assembled by torch so the cotangent reaches it)
+            u0 = torch.cat([z, torch.zeros(n, S - D, device=dev, dtype=torch.float32)], dim=1)
+        u1 = _Solve.apply(u0, ps, icnf, mode, e, y, t1, t0, icnf._group(group))
+        return u1[:, :icnf.nvariables].t()
     alg = icnf._solver()
     if icnf.adaptive:
         u1 = _adaptive_integrate(icnf, h, u0, t1, t0, e, y, group=icnf._group(group))

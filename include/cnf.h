@@ -32,10 +32,11 @@
  *                            cnf_vcabm_begin / _attempt / _accept / _state, cnf_solve_vcabm (the reference's default alg VCABM), cnf_solve_tsit5,
  *                            cnf_loss_adaptive (the whole `loss` call under either)
  *   training                 cnf_loss_grad_fixed, cnf_loss_grad_grid, cnf_loss_grad_adaptive  (dloss/dps, optionally dloss/dxs)
+ *   pullback of the solve    cnf_integrate_fixed_vjp, cnf_integrate_grid_vjp  (any cotangent of the final state -> dps, du0)
  *   column shards (RCCL)     cnf_comm_unique_id, cnf_comm_init, cnf_comm_init_all, cnf_comm_destroy, cnf_comm_rank, cnf_comm_size,
  *                            cnf_allreduce_loss (the mean in `loss`), cnf_allreduce_sum, cnf_comm_group_start / _end
  *   tuning (A/B, tests)      cnf_get_tuning, cnf_set_tuning
- *   introspection            cnf_version, cnf_build_info, cnf_last_error, cnf_kernel_path, cnf_kernel_family, cnf_grad_path, cnf_grad_path_for, cnf_grad_form_for, cnf_repack_on_device, cnf_solve_controller
+ *   introspection            cnf_version, cnf_build_info, cnf_last_error, cnf_kernel_path, cnf_kernel_family, cnf_grad_path, cnf_grad_path_for, cnf_grad_form_for, cnf_vjp_path_for, cnf_repack_on_device, cnf_solve_controller
  */
 #ifndef CNF_H
 #define CNF_H
@@ -430,6 +431,39 @@ int cnf_grad_path_for(const cnf_handle* h, int64_t B, int alg, int on_grid);
  * sample and stage of HBM, bounded by cnf_tuning.coop_grad3_gib), the sweep (cnf_coop_grad3.hip) runs the second-order chains
  * alone, the weight cotangents are products over tiles (cnf_wgrad_tiles.hip).  Same gradient to rounding. */
 int cnf_grad_form_for(const cnf_handle* h, int64_t B, int alg, int nsteps, int on_grid);
+
+/* ---- the pullback of base_sol ---------------------------------------------------------------------------------------------
+ * cnf_loss_grad_* differentiate ONE functional, sum_j (-logp_j + l1 E_j + l2 n_j + l3 A_j) under the standard normal.  These
+ * entries are the primitive underneath it - what the reference's ZygoteVJP pullback of `solve` is (src/core/icnf.jl:90-99): given
+ * a cotangent of the final state u1 they return the cotangents of the parameters and of the initial state u0, so a caller can
+ * differentiate any scalar built on the solve (another base distribution, per-sample weights, a logsumexp over flows, a loss on
+ * generated samples).  On the fixed-step grid of cnf_integrate_fixed:
+ *   u1 = integrate(u0; p)                                             the same discrete solve, S x B
+ *   grad[k]     = sum_{r,j} u1_bar[r,j] d u1[r,j] / d p[k]             layout of cnf_set_params' p, overwritten
+ *   u0_bar[r,j] = sum_{r'}  u1_bar[r',j] d u1[r',j] / d u0[r,j]        S x B, may be NULL
+ *   u1 (S x B, may be NULL): the forward result of that solve.
+ * u0, u1_bar: device, S x B.  t1 < t0 integrates backwards (generate).  B = 0 zeroes grad.  u0_bar and u1 may not alias the inputs
+ * or each other.  Rows D .. D+2 of u0_bar equal those of u1_bar (those rows feed nothing).  A row the handle does not compute (E
+ * without reg_z, n without reg_j, both in EXACT mode) is constant along the solve and its cotangent is ignored.  The shipped
+ * gradient is this call with u1_bar = [z1 + l3 z_aug / |z_aug|; 1; l1; l2].  Deterministic: fixed-order sums, no float atomics.
+ * Stateless: the call runs its own checkpointing forward solve; nothing is kept in the handle for a later call.  A shard's grad is
+ * a partial sum over its columns, which the caller all-reduces.
+ * Two implementations (cnf_vjp_path_for): 1 = the fused per-wave reverse sweep in its cotangent form (csrc/cnf_grad2_cot.hip) for
+ * one-probe VJP handles of the fused gradient's shapes (tanh / softplus, 2 or 3 equal hidden layers of at most 64, D + 1 <= 15,
+ * with and without conditions), on uniform steps and on a grid; 2 = the layer-wise reverse sweep (csrc/cnf_layered.hip) for every
+ * other Dense chain: JVP mode, several probes, the exact trace, the other activations, and the shapes whose shipped gradient runs
+ * on the slab-accumulator kernel or the cooperative sweeps - those kernels have no cotangent form, so such shapes are correct but
+ * layer-wise here; 0 = none (a layer wider than the product kernels cover): CNF_ERR_UNSUPPORTED. */
+int cnf_integrate_fixed_vjp(cnf_handle* h, int alg, int nsteps, float t0, float t1, const float* u0, const float* eps,
+                            const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1,
+                            void* stream);
+/* The same on the caller's grid (tgrid: HOST array of nsteps + 1 times), as cnf_loss_grad_grid: the pullback of a solve whose
+ * accepted adaptive steps were frozen. */
+int cnf_integrate_grid_vjp(cnf_handle* h, int alg, int nsteps, const float* tgrid, const float* u0, const float* eps,
+                           const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1,
+                           void* stream);
+/* Which implementation such a call takes: 1 fused per-wave sweep, 2 layer-wise, 0 none (the call returns CNF_ERR_UNSUPPORTED). */
+int cnf_vjp_path_for(const cnf_handle* h, int64_t B, int alg, int on_grid);
 
 /* ---- column shards: the one exchange step of the path -----------------------------------------
  * Under fixed-step integration every column (sample) is independent (src/core/icnf.jl:530-535 is column-wise), so rank r
