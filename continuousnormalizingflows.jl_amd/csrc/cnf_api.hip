@@ -209,11 +209,11 @@ int cnf_create(cnf_handle** out, const cnf_config* cfg) {
         }
     }
     const bool jvp_twin = c.mode == CNF_MODE_HUTCH_JVP && !c.reg_j && tuning().jvp_grad_twin != 0;
-    // (the one-probe twin of a K-probe VJP handle serves only handles whose OWN gradient is not fused - grad_serve never picks it
+    // (the one-probe twin of a K-probe VJP handle serves only handles whose OWN gradient is not fused - api_grad_call never picks it
     // otherwise: cfg3, whose gradient is the fused K-probe sweep, gets none, and with it no second plan, image and per-update repack;
     // ADVICE r5)
     const bool probe_twin = c.mode == CNF_MODE_HUTCH_VJP && c.nprobes > 1 && tuning().probe_grad_twin != 0 &&
-                            api_grad_route(h, -1, CNF_ALG_TSIT5, false).path != 1;
+                            api_grad_call(h, -1, CNF_ALG_TSIT5, false).path != 1;
     if ((jvp_twin || probe_twin) && c.kernel_path == CNF_PATH_AUTO && c.arith == CNF_ARITH_F32) {
         // the gradient twin (cnf_handle.h); CNF_JVP_GRAD_TWIN=0 / CNF_PROBE_GRAD_TWIN=0 keep the configuration's own gradient (tests, A/B).
         // A JVP handle with several probes gets the K-probe VJP twin, which gets its own one-probe twin here in turn.

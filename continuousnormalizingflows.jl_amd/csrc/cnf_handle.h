@@ -177,16 +177,16 @@ int api_integrate_grid(cnf_handle* h, int alg, int nsteps, const float* tgrid, f
                        int64_t B, hipStream_t st);
 // cnf_api_grad.hip
 cnf_config api_grad_cfg(const cnf_handle* h);
-bool api_grad_is_fused(const cnf_handle* h);
-bool api_grad_uses_slab(const cnf_handle* h);
-bool api_grad_uses_coop_aux(const cnf_handle* h, int64_t B);   // the auxiliary cooperative plan serves this batch size
-// which gradient implementation serves a call of B columns with `alg` on uniform steps / on a caller's grid (cnf_grad_path_for)
-struct GradRoute {
-    int path = 0;              // 0 none, 1 fused per-wave (register or slab accumulators), 2 layer-wise, 3 cooperative reverse sweep
-    bool slab = false;         // path 1 on the slab-accumulator kernel
-    bool use_cg_aux = false;   // path 3 on the handle's auxiliary cooperative plan (plan_cg / cg_packed)
+// one gradient call, resolved: who serves a call of B columns (B < 0: not known) with `alg` on uniform steps / on a caller's grid, and how
+struct GradCall {
+    cnf_handle* srv = nullptr;      // the handle whose implementation runs: the one asked, or a twin of it (cnf_handle::grad_twin)
+    int nloop = 1;                  // K > 1: srv is the one-probe twin, called once per probe
+    int path = 0;                   // 0 none, 1 fused per-wave (register or slab accumulators), 2 layer-wise, 3 cooperative reverse sweep
+    bool slab = false;              // path 1 on the slab-accumulator kernel
+    MfmaPlan* plan = nullptr;       // srv's plan and operand image for the route: on path 3 the auxiliary cooperative pair
+    const float* image = nullptr;   // (grad.plan_cg / cg_packed) where that one serves the batch; the forward pair otherwise
 };
-GradRoute api_grad_route(const cnf_handle* h, int64_t B, int alg, bool on_grid);
+GradCall api_grad_call(const cnf_handle* h, int64_t B, int alg, bool on_grid);
 // cnf_api_adaptive.hip
 int api_ensure_adaptive_buf(cnf_handle* h, int64_t B);
 // `ck` (may be null): checkpoint arrays the one-launch solve fills for its accepted steps - z_n per step (cap + 1 slots), the six stage
