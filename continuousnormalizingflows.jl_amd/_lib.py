@@ -38,7 +38,8 @@ EXPORTS = ("cnf_version", "cnf_build_info", "cnf_get_tuning", "cnf_set_tuning", 
            "cnf_comm_unique_id", "cnf_comm_init", "cnf_comm_init_all", "cnf_comm_destroy", "cnf_comm_rank", "cnf_comm_size",
            "cnf_comm_group_start", "cnf_comm_group_end", "cnf_allreduce_loss", "cnf_allreduce_sum",
            "cnf_kernel_family", "cnf_kernel_family_for", "cnf_kernel_name", "cnf_grad_path_for", "cnf_grad_form_for",
-           "cnf_integrate_fixed_vjp", "cnf_integrate_grid_vjp", "cnf_vjp_path_for")
+           "cnf_integrate_fixed_vjp", "cnf_integrate_grid_vjp", "cnf_vjp_path_for",
+           "cnf_integrate_fixed_vjp_cond", "cnf_integrate_grid_vjp_cond")
 FAMILY_SIMT, FAMILY_PER_WAVE, FAMILY_COOP, FAMILY_COOPX, FAMILY_TILE_SPLIT, FAMILY_LAYERED, FAMILY_COOPD = 0, 1, 2, 3, 4, 5, 6
 FAMILY_NAMES = ("simt", "per_wave", "coop", "coopx", "tile_split", "layered", "coopd")
 
@@ -148,6 +149,8 @@ def load():
                                         C.POINTER(C.c_float), fp, fp, fp, vp]
     lib.cnf_integrate_fixed_vjp.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, fp, C.c_int64, fp, fp, fp, fp, vp]
     lib.cnf_integrate_grid_vjp.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), fp, fp, fp, C.c_int64, fp, fp, fp, fp, vp]
+    lib.cnf_integrate_fixed_vjp_cond.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, fp, C.c_int64, fp, fp, fp, fp, fp, vp]
+    lib.cnf_integrate_grid_vjp_cond.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), fp, fp, fp, C.c_int64, fp, fp, fp, fp, fp, vp]
     lib.cnf_vjp_path_for.argtypes = [vp, C.c_int64, C.c_int, C.c_int]
     lib.cnf_comm_unique_id.argtypes = [vp]
     lib.cnf_comm_init.argtypes = [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int]

@@ -1,4 +1,4 @@
-// cnf_api_grad.hip — the gradient entry points of the C ABI (include/cnf.h): cnf_loss_grad_fixed / _grid / _adaptive, cnf_grad_path, cnf_integrate_*_vjp.
+// cnf_api_grad.hip — the gradient entry points of the C ABI (include/cnf.h): cnf_loss_grad_fixed / _grid / _adaptive, cnf_grad_path, cnf_integrate_*_vjp[_cond].
 // In file order: who serves a call (api_grad_call: ONE resolved GradCall per call), the layouts of the gradient workspace (FusedWs, SharedWs), the
 // checkpointing forward pass of the per-wave kernels (ckpt_forward), one function per implementation (grad_fused / _slab / _coop / _layered), the entries.
 #include "cnf_handle.h"
@@ -126,8 +126,9 @@ int cnf_grad_form_for(const cnf_handle* h, int64_t B, int alg, int nsteps, int o
 // Layout of the fused per-wave gradient's workspace (cnf_handle::grad.ws) for `steps` steps: z checkpoints (steps + 1 slots), stage
 // derivatives (steps x stages slots), logp + regs (4 B), the gradient slabs, the ping-pong states of a grid's step-by-step forward
 // pass, the unit probes of TestMode.  The regions as offsets into the buffer, once it holds need_floats; `zslot`: floats of one slot.
-struct FusedWs { size_t ckpt, ckpt_k, logp, regs, slab, states, unit, zslot, unit_floats, need_floats; };
-static FusedWs fused_ws(cnf_handle* h, int alg, int steps, int64_t B, bool on_grid) {
+// `yimg` (asked for by the pullback with ys_bar only, behind everything else): the image of W_1[:, ycols]^T, packed per call.
+struct FusedWs { size_t ckpt, ckpt_k, logp, regs, slab, states, unit, zslot, unit_floats, need_floats, yimg; };
+static FusedWs fused_ws(cnf_handle* h, int alg, int steps, int64_t B, bool on_grid, bool with_yimg = false) {
     FusedWs W{};
     const int nstages = alg == CNF_ALG_RK4 ? 4 : 6;
     W.zslot = (size_t)((B + 15) / 16) * 64 * (size_t)mfma_plan_zr(h->plan);
@@ -139,6 +140,7 @@ static FusedWs fused_ws(cnf_handle* h, int alg, int steps, int64_t B, bool on_gr
     W.unit = W.states + (on_grid ? 2 * (size_t)h->S * (size_t)B : 0);
     W.unit_floats = h->cfg.mode == CNF_MODE_EXACT ? (size_t)h->D * (size_t)h->D * (size_t)B : 0;
     W.need_floats = W.unit + W.unit_floats;
+    if (with_yimg) { W.yimg = (W.need_floats + 63) / 64 * 64; W.need_floats = W.yimg + grad_yimg_floats(); }
     return W;
 }
 
@@ -517,6 +519,8 @@ int cnf_loss_grad_adaptive(cnf_handle* h, float t0, float t1, const float* x, co
 // for the one-probe VJP shapes of cnf_grad.hip's table, the layer-wise sweep (cnf_layered.hip) for every other Dense chain - JVP mode,
 // several probes, the exact trace, the slab and cooperative shapes (their kernels have no cotangent form).  Nothing is kept in the
 // handle between calls beyond workspace capacity.
+// ys_bar (cnf_integrate_*_vjp_cond; null: the call is bit for bit the one without it): the cotangent of the conditions, on the same
+// routes - path 1 on the kernel of cnf_grad2_coty.hip, path 2 with one more accumulation per stage and one product per call.
 static int vjp_route(const cnf_handle* h) {
     const cnf_config& c = h->cfg;
     if (grad_is_fused(h) && (h->grad.packed || !h->par.have) && c.mode == CNF_MODE_HUTCH_VJP && c.nprobes == 1) return 1;
@@ -525,7 +529,7 @@ static int vjp_route(const cnf_handle* h) {
 
 static int integrate_vjp_impl(cnf_handle* h, const char* who, int alg, int nsteps, float t0, float t1, const float* tgrid, const float* u0,
                               const float* eps, const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1,
-                              void* stream) {
+                              void* stream, float* ys_bar = nullptr) {
     int rc = api_check_call(h, eps, ys, B, who);
     if (rc) return rc;
     const std::string w(who);
@@ -534,6 +538,9 @@ static int integrate_vjp_impl(cnf_handle* h, const char* who, int alg, int nstep
     if ((B > 0 && (!u0 || !u1_bar)) || !grad) return fail(CNF_ERR_INVALID, w + ": null u0/u1_bar/grad");
     if (B > 0 && ((u0_bar && (u0_bar == u0 || u0_bar == u1_bar || u0_bar == u1)) || (u1 && (u1 == u0 || u1 == u1_bar))))
         return fail(CNF_ERR_INVALID, w + ": u0_bar / u1 may not alias u0, u1_bar or each other");
+    if (ys_bar && h->cfg.ncond == 0) return fail(CNF_ERR_INVALID, w + ": ys_bar given, but the handle has no conditions");
+    if (ys_bar && B > 0 && (ys_bar == ys || ys_bar == u0 || ys_bar == u1_bar || ys_bar == u0_bar || ys_bar == u1))
+        return fail(CNF_ERR_INVALID, w + ": ys_bar may not alias ys, u0, u1_bar, u0_bar or u1");
     const int path = vjp_route(h);
     if (path == 0) return fail(CNF_ERR_UNSUPPORTED, w + ": no pullback for this configuration (a layer wider than the product kernels cover)");
     DeviceGuard g(h->cfg.device_id);
@@ -545,7 +552,7 @@ static int integrate_vjp_impl(cnf_handle* h, const char* who, int alg, int nstep
     if (tgrid) { t0 = tgrid[0]; t1 = tgrid[nsteps]; }
     if (path == 2) {
         std::string msg;
-        const LayeredCot cot{u0, u1_bar, u0_bar, u1};
+        const LayeredCot cot{u0, u1_bar, u0_bar, u1, ys_bar};
         hipError_t e = layered_grad(&h->grad.layered, h->cfg, h->par.P_dev, h->par.w_off.data(), h->par.b_off.data(), nullptr, eps, ys, alg, nsteps,
                                     t0, t1, tgrid, B, sw, grad, nullptr, st, &msg, nullptr, nullptr, &cot);
         if (e == hipErrorNotSupported) return fail(CNF_ERR_UNSUPPORTED, w + ": " + msg);
@@ -558,7 +565,7 @@ static int integrate_vjp_impl(cnf_handle* h, const char* who, int alg, int nstep
         if (rc) return rc;
     }
     HIP_TRY(api_num_cus(h));
-    const FusedWs W = fused_ws(h, alg, nsteps, B, tgrid != nullptr);
+    const FusedWs W = fused_ws(h, alg, nsteps, B, tgrid != nullptr, ys_bar != nullptr);
     HIP_TRY(h->grad.ws.reserve(W.need_floats));
     float* ws = h->grad.ws;
     // the checkpointing forward solve from the caller's full state
@@ -566,7 +573,8 @@ static int integrate_vjp_impl(cnf_handle* h, const char* who, int alg, int nstep
     rc = ckpt_forward(h, alg, nsteps, t0, t1, tgrid, eps, ys, B, p, st);
     if (rc) return rc;
     HIP_TRY(grad_launch(api_grad_cfg(h), h->grad.packed, ws + W.ckpt, ws + W.ckpt_k, mfma_plan_zr(h->plan), eps, ys, h->par.w_off.data(), h->par.b_off.data(), alg,
-                        nsteps, t0, t1, tgrid_dev, 0.f, B, sw, ws + W.slab, grad, nullptr, h->num_cus, st, u1_bar, u0_bar));
+                        nsteps, t0, t1, tgrid_dev, 0.f, B, sw, ws + W.slab, grad, nullptr, h->num_cus, st, u1_bar, u0_bar, ys_bar,
+                        ys_bar ? (const float*)h->par.P_dev : nullptr, ys_bar ? ws + W.yimg : nullptr));
     return CNF_OK;
 }
 
@@ -581,6 +589,17 @@ int cnf_integrate_grid_vjp(cnf_handle* h, int alg, int nsteps, const float* tgri
                            int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1, void* stream) {
     if (nsteps < 1 || !tgrid) return fail(CNF_ERR_INVALID, "cnf_integrate_grid_vjp: nsteps >= 1 and a grid of nsteps + 1 times required");
     return integrate_vjp_impl(h, "cnf_integrate_grid_vjp", alg, nsteps, 0.f, 0.f, tgrid, u0, eps, ys, B, u1_bar, grad, u0_bar, u1, stream);
+}
+
+int cnf_integrate_fixed_vjp_cond(cnf_handle* h, int alg, int nsteps, float t0, float t1, const float* u0, const float* eps, const float* ys,
+                                 int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* ys_bar, float* u1, void* stream) {
+    return integrate_vjp_impl(h, "cnf_integrate_fixed_vjp_cond", alg, nsteps, t0, t1, nullptr, u0, eps, ys, B, u1_bar, grad, u0_bar, u1, stream, ys_bar);
+}
+
+int cnf_integrate_grid_vjp_cond(cnf_handle* h, int alg, int nsteps, const float* tgrid, const float* u0, const float* eps, const float* ys,
+                                int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* ys_bar, float* u1, void* stream) {
+    if (nsteps < 1 || !tgrid) return fail(CNF_ERR_INVALID, "cnf_integrate_grid_vjp_cond: nsteps >= 1 and a grid of nsteps + 1 times required");
+    return integrate_vjp_impl(h, "cnf_integrate_grid_vjp_cond", alg, nsteps, 0.f, 0.f, tgrid, u0, eps, ys, B, u1_bar, grad, u0_bar, u1, stream, ys_bar);
 }
 
 int cnf_vjp_path_for(const cnf_handle* h, int64_t B, int alg, int on_grid) {

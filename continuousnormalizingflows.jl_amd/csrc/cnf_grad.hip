@@ -81,6 +81,16 @@ grad_reduce_kernel(const float* __restrict__ slab, int nwaves, GArgs a, float* _
     }
 }
 
+// The A image of W_1[:, ycols]^T (C x H: one M tile, HT k-groups) for the ys_bar product of cnf_grad2_coty.hip, gathered from the
+// Lux-layout device parameters: img[(kg * 64 + lane) * 4 + j] = W_1[16 kg + 4 j + (lane >> 4), ycol + rowmap(0, lane & 15)]
+__global__ void pack_ycols_t_kernel(const float* __restrict__ lux, float* __restrict__ img, int HT, int H, int C, long long w0, int ycol) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= HT * 256) return;
+    const int j = e & 3, lane = (e >> 2) & 63, kg = e >> 8;
+    const int row = mfma_rowmap(0, lane & 15), k = 16 * kg + 4 * j + (lane >> 4);
+    img[e] = (row < C && k < H) ? lux[w0 + k + (long long)H * (ycol + row)] : 0.f;
+}
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
@@ -118,6 +128,7 @@ static const GradInst* grad_find(const cnf_config& c) {
 bool grad_supported(const cnf_config& c) { return grad_find(c) != nullptr; }
 size_t grad_packed_bytes(const cnf_config& c) { return (size_t)grad_find(c)->packed_floats * sizeof(float); }
 size_t grad_slab_floats(const cnf_config& c, int num_cus) { return (size_t)num_cus * 4 * grad_find(c)->slab_total; }
+size_t grad_yimg_floats() { return (size_t)MfmaLayout::imgA(1, 4); }   // the widest shape of the table: 4 hidden tiles
 void grad_shape(const cnf_config& c, int* HT, int* L, int* ZR, int* CR) {
     const GradInst* g = grad_find(c);
     *HT = g->HT; *L = g->L; *ZR = g->ZR; *CR = g->CR;
@@ -127,11 +138,13 @@ hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float
                        int ckpt_zr, const float* eps, const float* ys,
                        const size_t* w_off, const size_t* b_off, int alg, int nsteps, float t0, float t1, const float* tgrid_dev,
                        float probe_w, long long B, const float lam[3], float* slab, float* grad, float* grad_x, int num_cus, hipStream_t st,
-                       const float* u1_bar, float* u0_bar) {
+                       const float* u1_bar, float* u0_bar, float* ys_bar, const float* lux_dev, float* y_img) {
     const GradInst* gi = grad_find(c);
     if (!gi) return hipErrorNotSupported;
     const bool cot = u1_bar != nullptr;   // the pullback of the solve (cnf_grad2_cot.hip): one probe only
     if (cot && c.nprobes != 1) return hipErrorNotSupported;
+    const bool coty = ys_bar != nullptr;  // ... with the cotangent of the conditions (cnf_grad2_coty.hip)
+    if (coty && (!cot || gi->CR == 0 || !lux_dev || !y_img)) return hipErrorNotSupported;
     // > 64 KB of dynamic LDS has to be enabled once per device and kernel
     const int idx = (int)(gi - kGrad);
     int dev = 0;
@@ -139,13 +152,15 @@ hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float
     if (e0 != hipSuccess) return e0;
     // one probe / several probes (the probe loop rolled around the pullback and its bottom-up reverse): cnf_grad2.hip compiled twice
     if (!ckpt_k) return hipErrorNotSupported;   // the sweep reads the forward kernel's stage checkpoints
-    const GradCotKernel kern_cot = cot ? grad2_cot_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : nullptr;
+    const GradCotYKernel kern_coty = coty ? grad2_coty_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : nullptr;
+    const GradCotKernel kern_cot = cot && !coty ? grad2_cot_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : nullptr;
     const GradKernel kern = cot ? nullptr : c.nprobes == 1 ? grad2_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT) : grad2_probes_kernel(gi->HT, gi->L, gi->ZR, gi->CR, gi->ACT);
-    if (!kern && !kern_cot) return hipErrorNotSupported;
-    static DeviceOnce done_one[sizeof(kGrad) / sizeof(kGrad[0])], done_probes[sizeof(kGrad) / sizeof(kGrad[0])], done_cot[sizeof(kGrad) / sizeof(kGrad[0])];
-    DeviceOnce& done = (cot ? done_cot : c.nprobes > 1 ? done_probes : done_one)[idx];
+    if (!kern && !kern_cot && !kern_coty) return hipErrorNotSupported;
+    static DeviceOnce done_one[sizeof(kGrad) / sizeof(kGrad[0])], done_probes[sizeof(kGrad) / sizeof(kGrad[0])], done_cot[sizeof(kGrad) / sizeof(kGrad[0])],
+        done_coty[sizeof(kGrad) / sizeof(kGrad[0])];
+    DeviceOnce& done = (coty ? done_coty : cot ? done_cot : c.nprobes > 1 ? done_probes : done_one)[idx];
     if (!done.done(dev)) {
-        hipError_t e = hipFuncSetAttribute(cot ? (const void*)kern_cot : (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, gi->lds_bytes);
+        hipError_t e = hipFuncSetAttribute(coty ? (const void*)kern_coty : cot ? (const void*)kern_cot : (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, gi->lds_bytes);
         if (e != hipSuccess) return e;
         done.set(dev);
     }
@@ -162,7 +177,15 @@ hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float
     const int nwaves = nblocks * 4;
     hipError_t e = zero_async(slab, (size_t)nwaves * gi->slab_total * sizeof(float), st);
     if (e != hipSuccess) return e;
-    if (cot) {
+    if (coty) {
+        hipLaunchKernelGGL(pack_ycols_t_kernel, dim3(gi->HT), dim3(256), 0, st, lux_dev, y_img, gi->HT, a.H, a.C, (long long)w_off[0], a.D + (a.autonomous ? 0 : 1));
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        GArgsCotY ay{};
+        static_cast<GArgs&>(ay) = a;
+        ay.u1_bar = u1_bar; ay.u0_bar = u0_bar; ay.y_img = y_img; ay.ys_bar = ys_bar;
+        hipLaunchKernelGGL(kern_coty, dim3(nblocks), dim3(256), gi->lds_bytes, st, ay);
+    } else if (cot) {
         GArgsCot ac{};
         static_cast<GArgs&>(ac) = a;
         ac.u1_bar = u1_bar; ac.u0_bar = u0_bar;

@@ -23,13 +23,17 @@
 #include "cnf_grad_dev.h"
 #include "cnf_sched_dev.h"
 
-// compiled three times: cnf_grad2.hip (one probe), cnf_grad2_probes.hip (-DG2_MULTI=true: several probes) and cnf_grad2_cot.hip
-// (-DG2_COT=true: one probe, the terminal costate and the row cotangents from the caller)
+// compiled four times: cnf_grad2.hip (one probe), cnf_grad2_probes.hip (-DG2_MULTI=true: several probes), cnf_grad2_cot.hip
+// (-DG2_COT=true: one probe, the terminal costate and the row cotangents from the caller) and cnf_grad2_coty.hip (G2_COT and
+// -DG2_YB=true: the cotangent form that also returns the cotangent of the conditions; conditioned shapes only)
 #ifndef G2_FIND
 #define G2_FIND grad2_kernel
 #endif
 #ifndef G2_COT
 #define G2_COT false
+#endif
+#ifndef G2_YB
+#define G2_YB false
 #endif
 #include <type_traits>
 
@@ -175,9 +179,14 @@ __device__ __forceinline__ StageCoef stage_coef(const float* tab, int st) {   //
 // COT: the pullback of the solve instead of the gradient of the shipped loss - the terminal costate is rows 0 .. D-1 of the caller's
 // u1_bar (no z_N, no l3 term), the cotangents of ldot / Edot / ndot are dt b_i times rows D .. D+2 of the lane's sample (three more
 // per-lane floats), and the costate at t0 goes to u0_bar with those three rows passed through.  Everything between is unchanged.
-template <int HT, int L, int ZR, int CR, int ACT, bool MULTI, bool COT>
+// YB (a cotangent form): ys_bar as well.  The conditions enter layer one as W_1[:, ycols] y, constant over the solve, so their cotangent
+// is W_1[:, ycols]^T applied to the sum over every stage of every step of abar_1 - the full cotangent of layer one's pre-activation,
+// first- and second-order chain alike, already scaled by dt b_i through kbar.  The sum is kept in HT accumulator tiles per sample tile
+// (cy) and multiplied once, after the step loop, by the image a.y_img (fragments from global memory: 4 HT MFMAs a tile and solve).
+template <int HT, int L, int ZR, int CR, int ACT, bool MULTI, bool COT, bool YB = false>
 __global__ void __launch_bounds__(256)
-mfma_grad2_kernel(std::conditional_t<COT, GArgsCot, GArgs> a) {
+mfma_grad2_kernel(std::conditional_t<YB, GArgsCotY, std::conditional_t<COT, GArgsCot, GArgs>> a) {
+    static_assert(!YB || (COT && !MULTI && CR > 0), "ys_bar: the one-probe cotangent form of a conditioned shape");
     using G = GradLds<HT, L, ZR, CR, ACT>;
     using SL = GradSlab<HT, L, ZR, CR>;
     constexpr MfmaLayout LAY(HT, L, ZR, CR, true, 0);
@@ -282,6 +291,8 @@ mfma_grad2_kernel(std::conditional_t<COT, GArgsCot, GArgs> a) {
             }
         }
 
+        f32x4 cy[YB ? HT : 1];   // ys_bar: sum of abar_1 over the stages of this tile's solve (zeroed per tile: a wave may walk several)
+        if constexpr (YB) zero_tiles<HT>(cy);
         // step checkpoints (z_n and the stage derivatives kz_i, z rows, written by the forward kernel): requested one STEP ahead -
         // a step opened with an exposed HBM round trip otherwise
         float zn[ZR], kz[6][ZR];
@@ -597,6 +608,7 @@ mfma_grad2_kernel(std::conditional_t<COT, GArgsCot, GArgs> a) {
                         const f32x4 d1 = dact(l, mt, one_t);
                         if constexpr (ACT == CNF_ACT_TANH) ab[mt] = d1 * __builtin_elementwise_fma(h[l][mt] * a2[l][mt], f32x4{-2.f, -2.f, -2.f, -2.f}, hb[mt]);
                         else ab[mt] = hb[mt] * d1 + a2[l][mt] * (d1 * (1.f - d1));
+                        if constexpr (YB && l == 0) cy[mt] += ab[mt];
                     }
                     if constexpr (l > 0) {
                         // Wbar_{l+1} += abar_l h_{l-1}^T;  bbar_{l+1} += row sums of abar_l;  hbar_{l-1} = W_{l+1}^T abar_l
@@ -706,6 +718,18 @@ mfma_grad2_kernel(std::conditional_t<COT, GArgsCot, GArgs> a) {
                     for (int r = 0; r < 3; ++r) a.u0_bar[smp * (D + 3) + D + r] = ub[r];
                 }
             }
+            if constexpr (YB) {   // ys_bar = W_1[:, ycols]^T cy: one M tile (C <= 16), row 4 r + g of the lane's sample in register r
+                f32x4 yb[1];
+                zero_tiles<1>(yb);
+                gemm_tiles<1, 4 * HT>(a.y_img, lane, TileIn<HT>{cy}, yb);
+                if (valid) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = 4 * r + g;
+                        if (f < a.C) a.ys_bar[smp * a.C + f] = yb[0][r];
+                    }
+                }
+            }
         } else if (a.grad_x && valid) {   // costate at t0 = dL/dz_0; its first nvars rows are dL/dx
 #pragma unroll
             for (int s = 0; s < ZR; ++s) {
@@ -747,7 +771,7 @@ mfma_grad2_kernel(std::conditional_t<COT, GArgsCot, GArgs> a) {
 // ---------------------------------------------------------------------------------------
 // host side: instance table (the launch itself is grad_launch's, cnf_grad.hip)
 // ---------------------------------------------------------------------------------------
-typedef std::conditional_t<G2_COT, GradCotKernel, GradKernel> G2Kernel;
+typedef std::conditional_t<G2_YB, GradCotYKernel, std::conditional_t<G2_COT, GradCotKernel, GradKernel>> G2Kernel;
 struct Grad2Inst {
     int HT, L, ZR, CR, ACT;
     G2Kernel kern;
@@ -755,7 +779,11 @@ struct Grad2Inst {
 #ifndef G2_MULTI
 #define G2_MULTI false
 #endif
+#if G2_YB
+#define G2_INST(HT, L, ZR, CR, ACT) Grad2Inst { HT, L, ZR, CR, ACT, &mfma_grad2_kernel<HT, L, ZR, CR, ACT, G2_MULTI, G2_COT, true> }
+#else
 #define G2_INST(HT, L, ZR, CR, ACT) Grad2Inst { HT, L, ZR, CR, ACT, &mfma_grad2_kernel<HT, L, ZR, CR, ACT, G2_MULTI, G2_COT> }
+#endif
 // the shapes of cnf_grad.hip's table (kGrad): 1 .. 4 hidden tiles, 2 / 3 hidden layers, D <= 8 / 16, with and without conditions
 #define G2_HT(HT, CR, ACT) G2_INST(HT, 3, 2, CR, ACT), G2_INST(HT, 2, 2, CR, ACT), G2_INST(HT, 3, 4, CR, ACT), G2_INST(HT, 2, 4, CR, ACT)
 #define G2_SHAPES(CR, ACT) G2_HT(1, CR, ACT), G2_HT(2, CR, ACT), G2_HT(3, CR, ACT), G2_HT(4, CR, ACT)

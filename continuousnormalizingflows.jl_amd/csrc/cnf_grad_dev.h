@@ -35,6 +35,13 @@ struct GArgsCot : GArgs {
     const float* u1_bar;
     float* u0_bar;         // or null
 };
+// The cotangent form that also returns the cotangent of the conditions (cnf_grad2_coty.hip, cnf_integrate_*_vjp_cond) - a struct of its
+// own for the same reason: GArgs and GArgsCot keep their bytes.  y_img: the A image (one M tile, HT k-groups: MfmaLayout::imgA(1, HT)
+// floats, global memory) of W_1[:, ycols]^T, which the shared operand layout does not carry; ys_bar: C x B, column-major like ys.
+struct GArgsCotY : GArgsCot {
+    const float* y_img;
+    float* ys_bar;
+};
 
 // Cross-wave exchange of accumulator-layout tiles through LDS.  A tile is stored with 8 dwords of
 // padding per 16-lane group (TS = 280 floats), which makes both transposed fragment reads below
@@ -147,5 +154,7 @@ GradKernel grad2_kernel(int HT, int L, int ZR, int CR, int ACT);
 GradKernel grad2_probes_kernel(int HT, int L, int ZR, int CR, int ACT);   // the same for several probes (cnf_grad2_probes.hip)
 typedef void (*GradCotKernel)(GArgsCot);
 GradCotKernel grad2_cot_kernel(int HT, int L, int ZR, int CR, int ACT);   // one probe, cotangent form (cnf_grad2_cot.hip)
+typedef void (*GradCotYKernel)(GArgsCotY);
+GradCotYKernel grad2_coty_kernel(int HT, int L, int ZR, int CR, int ACT);   // the same with ys_bar: conditioned shapes only (cnf_grad2_coty.hip)
 
 }  // namespace cnf

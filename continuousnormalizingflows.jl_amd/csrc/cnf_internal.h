@@ -116,15 +116,20 @@ hipError_t grad_launch(const cnf_config& c, const float* packed_dev, const float
                        int ckpt_zr, const float* eps, const float* ys,
                        const size_t* w_off, const size_t* b_off, int alg, int nsteps, float t0, float t1, const float* tgrid_dev,
                        float probe_w, long long B, const float lam[3], float* slab, float* grad, float* grad_x, int num_cus, hipStream_t st,
-                       const float* u1_bar = nullptr, float* u0_bar = nullptr);
+                       const float* u1_bar = nullptr, float* u0_bar = nullptr, float* ys_bar = nullptr, const float* lux_dev = nullptr,
+                       float* y_img = nullptr);
 // u1_bar (S x B): the cotangent form - the pullback of the solve whose checkpoints are given (one probe; lam[0] / lam[1] are then the
 // 0 / 1 switches of the E / n rows, lam[2] and grad_x unused); u0_bar (S x B or null) receives the cotangent of the initial state
+// ys_bar (C x B or null; conditioned shapes of the cotangent form): the cotangent of the conditions, on the kernel of cnf_grad2_coty.hip;
+// it reads W_1[:, ycols]^T from an image packed here from the Lux-layout device parameters lux_dev into y_img (grad_yimg_floats())
+size_t grad_yimg_floats();
 // layer-wise evaluation / gradient on the product kernels of cnf_lgemm.hip for everything the fused kernels do not cover (cnf_layered.hip)
 struct LayeredGrad;
 // the cotangent form of layered_grad (the pullback of the solve, cnf_integrate_*_vjp): the solve starts from u0 (S x B, all rows),
 // the terminal costate and the per-column cotangents of the dlogp / E / n rows come from u1_bar (S x B); u0_bar / u1 (S x B) or null.
 // x, lam[2], grad_x, logp_out and regs_out are then unused; lam[0] / lam[1] are the 0 / 1 switches of the E / n rows.
-struct LayeredCot { const float* u0; const float* u1_bar; float* u0_bar; float* u1; };
+// ys_bar (C x B or null): the cotangent of the conditions of a conditioned flow.
+struct LayeredCot { const float* u0; const float* u1_bar; float* u0_bar; float* u1; float* ys_bar; };
 bool layered_available();   // always: the products are the library's own kernels (cnf_lgemm.hip)
 bool layered_supports(const cnf_config& c);   // every layer within the product kernels' limits (512 outputs, 639 inputs)
 hipError_t layered_aug_f(LayeredGrad** ctx, const cnf_config& c, const float* P_dev, const size_t* w_off,

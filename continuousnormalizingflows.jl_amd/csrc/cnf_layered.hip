@@ -776,6 +776,10 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     const long long o_t0 = take(WB), o_t1 = take(WB), o_t2 = take(WB), o_t3 = take(WB), o_t4 = take(WB);
     long long o_z[CNF_MAX_LAYERS];   // pre-activations of the swish / GELU layers (recomputing mode; nothing for other layers)
     for (int l = 0; l < N; ++l) o_z[l] = act_dd_needs_pre(L.act[l]) && !keep_act ? take((long long)L.wout[l] * B) : -1;
+    // the pullback with ys_bar: the sum over all stages of sbar_1 (H_1 x B), taken last so that every other region keeps its place
+    float* const ys_bar = (cot && C > 0) ? cot->ys_bar : nullptr;
+    const long long H1B = (long long)L.wout[0] * B;
+    const long long o_ysum = ys_bar ? take(H1B) : 0;
     LG_HIP(G.ws.reserve((size_t)take.off));
     float* W = G.ws;
     float* PA = W + o_PA;
@@ -878,6 +882,8 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
     if (want_loss && cot) hipLaunchKernelGGL(cot_rows_init_kernel, grid_for(B), dim3(TPB), 0, st, lacc, eacc, nacc, cot->u0, D, B);
     else if (want_loss) LG_HIP(zero_async(lacc, 3 * (size_t)B * sizeof(float), st));
     const bool hutch = !exact;
+    float* const ysum = W + o_ysum;
+    if (ys_bar) LG_HIP(zero_async(ysum, (size_t)H1B * sizeof(float), st));
     int Gw = 1;                      // lanes per column of the grouped per-column kernels (0: D > 64, thread-per-column forms)
     while (Gw < D) Gw <<= 1;
     if (Gw > 64) Gw = 0;
@@ -993,6 +999,11 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
                     float* tmp = scur; scur = snxt; snxt = tmp;
                 } else {
                     LG_BLAS(gemm(OPT, OPN, D, B, L.wout[0], PA, L.wout[0], scur, L.wout[0], Zb[i], D));   // Zbar_i = W_1[:,0:D]^T sbar_1
+                    if (ys_bar) {   // the conditions' share of sbar_1 is constant over the solve: summed here, multiplied once at the end
+                        Comb cs{};
+                        cs.nk = 1; cs.k[0] = scur; cs.coef[0] = 1.f;
+                        hipLaunchKernelGGL(combine_kernel, grid_for(H1B), dim3(TPB), 0, st, ysum, ysum, cs, H1B);
+                    }
                 }
             }
         }
@@ -1002,6 +1013,8 @@ hipError_t layered_grad(LayeredGrad** ctx, const cnf_config& c, const float* P_d
         hipLaunchKernelGGL(combine_kernel, grid_for(DB), dim3(TPB), 0, st, lamv, lamv, cb, DB);
     }
     hipLaunchKernelGGL(reduce_slabs_kernel, grid_for(npa), dim3(TPB), 0, st, slabs, nslab, npa_pad, L, grad);
+    if (ys_bar)   // ys_bar = W_1[:, ycols]^T sum sbar_1 (the y columns follow z and, unless autonomous, the time column)
+        LG_BLAS(gemm(OPT, OPN, C, B, L.wout[0], PA + (long long)L.wout[0] * (D + (c.autonomous ? 0 : 1)), L.wout[0], ysum, L.wout[0], ys_bar, C));
     if (cot) {
         if (cot->u0_bar) hipLaunchKernelGGL(cot_out_kernel, grid_for((long long)(D + 3) * B), dim3(TPB), 0, st, cot->u0_bar, lamv, cot->u1_bar, D, B);
         if (cot->u1) hipLaunchKernelGGL(pack_final_kernel, grid_for(B), dim3(TPB), 0, st, cot->u1, zck + (long long)nsteps * DB, lacc, eacc, nacc, D, B);

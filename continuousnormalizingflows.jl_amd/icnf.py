@@ -608,8 +608,9 @@ def vjp_path(icnf: ICNF, mode: Mode, B: int, alg: int = _lib.ALG_TSIT5, on_grid:
 
 
 def _vjp_call(icnf: ICNF, h: _Handle, ps: torch.Tensor, u0c, e, y, alg: int, t0: float, t1: float, nsteps: int, tgrid, u1_bar_c,
-              want_u0_bar: bool = True, want_u1: bool = False):
-    """One library call on column-major (B, S) tensors: (gradient in ps's own layout, u0_bar or None, u1 or None)."""
+              want_u0_bar: bool = True, want_u1: bool = False, want_ys_bar: bool = False):
+    """One library call on column-major (B, S) tensors: (gradient in ps's own layout, u0_bar or None, u1 or None) - with
+    `want_ys_bar` (conditioned flows; the *_vjp_cond entries) also ys_bar, column-major (B, nconditions), as a fourth item."""
     dev = icnf.device
     B = u0c.shape[0]
     n_abi = ps.numel() if icnf.nn.planar is None else icnf.nn.abi_params(ps).numel()
@@ -617,6 +618,16 @@ def _vjp_call(icnf: ICNF, h: _Handle, ps: torch.Tensor, u0c, e, y, alg: int, t0:
     u0_bar = torch.empty_like(u0c) if want_u0_bar else None
     u1 = torch.empty_like(u0c) if want_u1 else None
     sp = _stream_ptr(dev)
+    if want_ys_bar:
+        ys_bar = torch.empty_like(y)
+        if tgrid is not None:
+            grid = (C.c_float * len(tgrid))(*tgrid)
+            _lib.check(h.lib.cnf_integrate_grid_vjp_cond(h.ptr, alg, len(tgrid) - 1, grid, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1_bar_c),
+                                                         _ptr(grad), _ptr(u0_bar), _ptr(ys_bar), _ptr(u1), sp))
+        else:
+            _lib.check(h.lib.cnf_integrate_fixed_vjp_cond(h.ptr, alg, nsteps, t0, t1, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1_bar_c),
+                                                          _ptr(grad), _ptr(u0_bar), _ptr(ys_bar), _ptr(u1), sp))
+        return grad[:ps.numel()], u0_bar, u1, ys_bar
     if tgrid is not None:
         grid = (C.c_float * len(tgrid))(*tgrid)
         _lib.check(h.lib.cnf_integrate_grid_vjp(h.ptr, alg, len(tgrid) - 1, grid, _ptr(u0c), _ptr(e), _ptr(y), B, _ptr(u1_bar_c),
@@ -628,13 +639,18 @@ def _vjp_call(icnf: ICNF, h: _Handle, ps: torch.Tensor, u0c, e, y, alg: int, t0:
 
 
 def integrate_vjp(icnf: ICNF, mode: Mode, u0: torch.Tensor, ps: torch.Tensor, u1_bar: torch.Tensor, *, t0: float, t1: float,
-                  eps: Optional[torch.Tensor], ys: Optional[torch.Tensor] = None, tgrid: Optional[Sequence[float]] = None):
+                  eps: Optional[torch.Tensor], ys: Optional[torch.Tensor] = None, tgrid: Optional[Sequence[float]] = None,
+                  want_ys_bar: bool = False):
     """The pullback of the fixed-step solve u1 = integrate(u0; ps) - what the reference's ZygoteVJP pullback of `solve` returns
     (src/core/icnf.jl:90-99): for a cotangent `u1_bar` ((S, B)) of the final state, `(grad_ps, u0_bar, u1)` with
     `grad_ps = u1_bar^T du1/dps`, `u0_bar = u1_bar^T du1/du0` ((S, B)) and the forward result `u1`.  The steps are those of
     `sol_kwargs` (`nsteps`, or `dt` with the tail step of the fixed-dt plan) from t0 to t1 - t1 < t0 integrates backwards as
     `generate` does - or the times of `tgrid`.  `eps` ((K*D, B)) are the Hutchinson probes of the solve (ignored in TestMode).
-    A shard's `grad_ps` is the partial sum over its columns."""
+    A shard's `grad_ps` is the partial sum over its columns.
+    `want_ys_bar=True` (conditioned flows): `(grad_ps, u0_bar, ys_bar, u1)` with `ys_bar = u1_bar^T du1/dys` ((nconditions, B)),
+    the cotangent of the conditions - per column, so a shard's `ys_bar` is complete for its columns."""
+    if want_ys_bar and not icnf.conditioned:
+        raise ValueError("integrate_vjp(want_ys_bar=True): the flow has no conditions (nconditions = 0)")
     if icnf._solver() == _lib.ALG_VCABM:
         raise NotImplementedError("integrate_vjp: VCABM has no one-step discrete adjoint; use Tsit5 or RK4 (the pullback of a "
                                   "frozen adaptive grid is the `tgrid` argument)")
@@ -650,6 +666,11 @@ def integrate_vjp(icnf: ICNF, mode: Mode, u0: torch.Tensor, ps: torch.Tensor, u1
     e = None if eps is None else _colmajor(eps, K * icnf.D, "eps", dev)
     y = _colmajor(ys, icnf.nconditions, "ys", dev) if icnf.conditioned else None
     grid, nsteps = _fixed_plan(icnf, t0, t1) if tgrid is None else ([float(t) for t in tgrid], 0)
+    if want_ys_bar:
+        if y.shape[0] != B:
+            raise ValueError("DimensionMismatch: u0 and ys must have the same number of columns")
+        g, u0_bar, u1, ys_bar = _vjp_call(icnf, h, ps, u0c, e, y, icnf._solver(), t0, t1, nsteps, grid, ubc, True, True, True)
+        return g, u0_bar.t(), ys_bar.t(), u1.t()
     g, u0_bar, u1 = _vjp_call(icnf, h, ps, u0c, e, y, icnf._solver(), t0, t1, nsteps, grid, ubc, True, True)
     return g, u0_bar.t(), u1.t()
 
@@ -667,7 +688,8 @@ def _fixed_plan(icnf: ICNF, t0: float, t1: float):
 class _Solve(torch.autograd.Function):
     """u1 = integrate(u0; ps) on column-major (B, S) states.  The forward is the library's plain solve; the backward is one
     cnf_integrate_*_vjp call on the current stream, on the steps the forward took (an adaptive Tsit5 solve: its accepted steps,
-    frozen).  Nothing is kept in the library's handle between the two."""
+    frozen).  Nothing is kept in the library's handle between the two.  The conditions `y` ((B, nconditions), column-major) are
+    a differentiable input when they require grad (cond_grad=True): the backward is then the *_vjp_cond call and returns ys_bar."""
 
     @staticmethod
     def forward(ctx, u0c, ps, icnf, mode, e, y, t0, t1, group):
@@ -704,25 +726,40 @@ class _Solve(torch.autograd.Function):
         icnf, mode, e, y, alg, t0, t1, nsteps, grid = ctx.rest
         h = icnf._handle(mode)
         icnf._bind_params(h, ps)
+        if y is not None and ctx.needs_input_grad[5]:
+            g, u0_bar, _, ys_bar = _vjp_call(icnf, h, ps, u0c, e, y, alg, t0, t1, nsteps, grid, u1_bar.contiguous().to(torch.float32),
+                                             ctx.needs_input_grad[0], False, True)
+            return u0_bar, (g if ctx.needs_input_grad[1] else None), None, None, None, ys_bar, None, None, None
         g, u0_bar, _ = _vjp_call(icnf, h, ps, u0c, e, y, alg, t0, t1, nsteps, grid, u1_bar.contiguous().to(torch.float32),
                                  ctx.needs_input_grad[0], False)
         return u0_bar, (g if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None
 
 
-def _check_differentiable(icnf: ICNF, ys, what: str):
+def _check_differentiable(icnf: ICNF, ys, what: str, cond_grad: bool = False):
     if icnf._solver() == _lib.ALG_VCABM:
         raise NotImplementedError(f"{what}(differentiable=True): VCABM has no one-step discrete adjoint here; use "
                                   "sol_kwargs alg=Tsit5() (adaptive or fixed-step) or RK4(), or loss_and_gradient, which "
                                   "differentiates the adaptive Tsit5 discretisation instead")
-    if ys is not None and getattr(ys, "requires_grad", False):
+    if not cond_grad and ys is not None and getattr(ys, "requires_grad", False):
         raise NotImplementedError(f"{what}(differentiable=True): no gradient with respect to ys; pass ys.detach() "
-                                  "(the conditions enter the solve as constants)")
+                                  "(the conditions enter the solve as constants), or cond_grad=True to differentiate with "
+                                  "respect to them")
 
 
-def _inference_differentiable(icnf: ICNF, mode: Mode, xs, ys, ps, eps, return_state: bool, group):
+def _check_cond_grad(icnf: ICNF, differentiable: bool, cond_grad: bool, what: str):
+    """cond_grad=True needs differentiable=True and a conditioned flow: refused before any library call."""
+    if not cond_grad:
+        return
+    if not differentiable:
+        raise ValueError(f"{what}(cond_grad=True) needs differentiable=True")
+    if not icnf.conditioned:
+        raise ValueError(f"{what}(cond_grad=True): the flow has no conditions (nconditions = 0)")
+
+
+def _inference_differentiable(icnf: ICNF, mode: Mode, xs, ys, ps, eps, return_state: bool, group, cond_grad: bool = False):
     """inference with the solve as an autograd node and the epilogue in plain torch: logp, E, n, A (and the state) carry
-    gradients to ps and xs."""
-    _check_differentiable(icnf, ys, "inference")
+    gradients to ps and xs - and, with cond_grad, to ys."""
+    _check_differentiable(icnf, ys, "inference", cond_grad)
     dev = icnf.device
     D, nv = icnf.D, icnf.nvariables
     if xs.dim() != 2 or xs.shape[0] != nv:
@@ -760,7 +797,8 @@ def _inference_differentiable(icnf: ICNF, mode: Mode, xs, ys, ps, eps, return_st
 
 
 def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
-              return_state: bool = False, _raw: bool = False, group=None, _sp=None, differentiable: bool = False):
+              return_state: bool = False, _raw: bool = False, group=None, _sp=None, differentiable: bool = False,
+              cond_grad: bool = False):
     """inference(icnf, mode, xs[, ys], ps, st) -> (logp̂x (B,), (Ė, ṅ, Ȧ)).
 
     `eps` ((K*D, B)) pins the Hutchinson probes; by default they are drawn from icnf.rng as
@@ -773,12 +811,15 @@ def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
     cnf_integrate_*_vjp) and the epilogue - log N(z) or `icnf.basedist.log_prob(z)`, minus dlogp; A = |z_aug| - is plain torch,
     so logp, E, n, A and the returned state carry gradients to `ps` and `xs`: any scalar built on them can be differentiated
     (sample weights, another base distribution, a logsumexp over flows).  Under an adaptive Tsit5 solver the backward runs on
-    the steps the forward accepted.  Not with VCABM, and not with respect to `ys`.  Each rank's gradient is the partial sum
-    of its own columns."""
+    the steps the forward accepted.  Not with VCABM.  With respect to `ys` only when `cond_grad=True` is given as well (a
+    conditioned flow whose conditions come from an encoder trained jointly with it): the backward then also returns the cotangent
+    of the conditions (cnf_integrate_*_vjp_cond); without it a `ys` that requires grad is refused.  Each rank's gradient is the
+    partial sum of its own columns (the gradient of `ys` is per column)."""
     xs, ys, ps, st = _split_args(icnf, args, "inference")
+    _check_cond_grad(icnf, differentiable, cond_grad, "inference")
     group = icnf._group(group)
     if differentiable:
-        return _inference_differentiable(icnf, mode, xs, ys, ps, eps, return_state, group)
+        return _inference_differentiable(icnf, mode, xs, ys, ps, eps, return_state, group, cond_grad)
     h = icnf._handle(mode)
     icnf._bind_params(h, ps)
     dev = icnf.device
@@ -828,11 +869,12 @@ def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
 
 
 def generate(icnf: ICNF, mode: Mode, *args, z0: Optional[torch.Tensor] = None,
-             eps: Optional[torch.Tensor] = None, group=None, differentiable: bool = False):
+             eps: Optional[torch.Tensor] = None, group=None, differentiable: bool = False, cond_grad: bool = False):
     """generate(icnf, mode, [ys,] ps, st, n) -> (nvariables, n) samples: integrate the base
     sample backwards over the reversed tspan (src/core/base_icnf.jl:351-404, 185-194).
     `differentiable=True`: the solve is a torch.autograd node (see `inference`), so the samples carry gradients to `ps` and to
-    `z0` - training on generated samples (reverse KL)."""
+    `z0` - training on generated samples (reverse KL) - and, with `cond_grad=True` on a conditioned flow, to `ys`."""
+    _check_cond_grad(icnf, differentiable, cond_grad, "generate")
     if icnf.conditioned:
         if len(args) != 4:
             raise TypeError("MethodError: generate(icnf, mode, ys, ps, st, n) expected")
@@ -843,7 +885,7 @@ def generate(icnf: ICNF, mode: Mode, *args, z0: Optional[torch.Tensor] = None,
         ps, st, n = args
         ys = None
     if differentiable:
-        _check_differentiable(icnf, ys, "generate")
+        _check_differentiable(icnf, ys, "generate", cond_grad)
     h = icnf._handle(mode)
     icnf._bind_params(h, ps)
     dev = icnf.device

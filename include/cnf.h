@@ -33,6 +33,7 @@
  *                            cnf_loss_adaptive (the whole `loss` call under either)
  *   training                 cnf_loss_grad_fixed, cnf_loss_grad_grid, cnf_loss_grad_adaptive  (dloss/dps, optionally dloss/dxs)
  *   pullback of the solve    cnf_integrate_fixed_vjp, cnf_integrate_grid_vjp  (any cotangent of the final state -> dps, du0)
+ *                            cnf_integrate_fixed_vjp_cond, cnf_integrate_grid_vjp_cond  (conditioned flows: dys as well)
  *   column shards (RCCL)     cnf_comm_unique_id, cnf_comm_init, cnf_comm_init_all, cnf_comm_destroy, cnf_comm_rank, cnf_comm_size,
  *                            cnf_allreduce_loss (the mean in `loss`), cnf_allreduce_sum, cnf_comm_group_start / _end
  *   tuning (A/B, tests)      cnf_get_tuning, cnf_set_tuning
@@ -462,7 +463,23 @@ int cnf_integrate_fixed_vjp(cnf_handle* h, int alg, int nsteps, float t0, float 
 int cnf_integrate_grid_vjp(cnf_handle* h, int alg, int nsteps, const float* tgrid, const float* u0, const float* eps,
                            const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* u1,
                            void* stream);
-/* Which implementation such a call takes: 1 fused per-wave sweep, 2 layer-wise, 0 none (the call returns CNF_ERR_UNSUPPORTED). */
+/* The pullback of the solve of a CONDITIONED flow with the cotangent of the conditions as well (a learned encoder ys = enc(context)
+ * trained jointly with the flow):
+ *   ys_bar[c,j] = sum_r u1_bar[r,j] d u1[r,j] / d ys[c,j]              C x B, column-major like ys, overwritten; may be NULL
+ * The conditions enter layer one as W_1[:, ycols] y_j, constant over the solve, so ys_bar_j = W_1[:, ycols]^T sum over the stages of
+ * all steps of the cotangent of layer one's pre-activation (first- and second-order chain), which both sweeps form anyway.  Only
+ * the C B floats of real columns are written.  With ys_bar == NULL the call IS cnf_integrate_*_vjp: same kernels, same bits.  With
+ * it: same routes (cnf_vjp_path_for), every configuration those entries serve; path 1 runs the kernel of csrc/cnf_grad2_coty.hip.
+ * ys_bar on an unconditioned handle, or aliasing ys, u0, u1_bar, u0_bar or u1: CNF_ERR_INVALID.  B = 0 zeroes grad and touches
+ * nothing else.  Deterministic and stateless like the entries above. */
+int cnf_integrate_fixed_vjp_cond(cnf_handle* h, int alg, int nsteps, float t0, float t1, const float* u0, const float* eps,
+                                 const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* ys_bar,
+                                 float* u1, void* stream);
+int cnf_integrate_grid_vjp_cond(cnf_handle* h, int alg, int nsteps, const float* tgrid, const float* u0, const float* eps,
+                                const float* ys, int64_t B, const float* u1_bar, float* grad, float* u0_bar, float* ys_bar,
+                                float* u1, void* stream);
+/* Which implementation such a call takes (with or without ys_bar): 1 fused per-wave sweep, 2 layer-wise, 0 none (the call returns
+ * CNF_ERR_UNSUPPORTED). */
 int cnf_vjp_path_for(const cnf_handle* h, int64_t B, int alg, int on_grid);
 
 /* ---- column shards: the one exchange step of the path -----------------------------------------
