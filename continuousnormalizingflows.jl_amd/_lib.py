@@ -39,7 +39,8 @@ EXPORTS = ("cnf_version", "cnf_build_info", "cnf_get_tuning", "cnf_set_tuning", 
            "cnf_comm_group_start", "cnf_comm_group_end", "cnf_allreduce_loss", "cnf_allreduce_sum",
            "cnf_kernel_family", "cnf_kernel_family_for", "cnf_kernel_name", "cnf_grad_path_for", "cnf_grad_form_for",
            "cnf_integrate_fixed_vjp", "cnf_integrate_grid_vjp", "cnf_vjp_path_for",
-           "cnf_integrate_fixed_vjp_cond", "cnf_integrate_grid_vjp_cond")
+           "cnf_integrate_fixed_vjp_cond", "cnf_integrate_grid_vjp_cond",
+           "cnf_f64_supported", "cnf_set_params_f64", "cnf_aug_f_f64", "cnf_integrate_fixed_f64", "cnf_inference_fixed_f64")
 FAMILY_SIMT, FAMILY_PER_WAVE, FAMILY_COOP, FAMILY_COOPX, FAMILY_TILE_SPLIT, FAMILY_LAYERED, FAMILY_COOPD = 0, 1, 2, 3, 4, 5, 6
 FAMILY_NAMES = ("simt", "per_wave", "coop", "coopx", "tile_split", "layered", "coopd")
 
@@ -152,6 +153,12 @@ def load():
     lib.cnf_integrate_fixed_vjp_cond.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, fp, C.c_int64, fp, fp, fp, fp, fp, vp]
     lib.cnf_integrate_grid_vjp_cond.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), fp, fp, fp, C.c_int64, fp, fp, fp, fp, fp, vp]
     lib.cnf_vjp_path_for.argtypes = [vp, C.c_int64, C.c_int, C.c_int]
+    # Float64 flows: the twins of cnf_set_params / cnf_aug_f / cnf_integrate_fixed / cnf_inference_fixed with double arrays and times
+    lib.cnf_f64_supported.argtypes = [vp]
+    lib.cnf_set_params_f64.argtypes = [vp, fp, C.c_size_t, szp, szp, C.c_int, vp]
+    lib.cnf_aug_f_f64.argtypes = [vp, fp, fp, C.c_double, fp, fp, C.c_int64, vp]
+    lib.cnf_integrate_fixed_f64.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, fp, fp, fp, C.c_int64, fp, vp]
+    lib.cnf_inference_fixed_f64.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, fp, fp, fp, C.c_int64, fp, fp, fp, vp]
     lib.cnf_comm_unique_id.argtypes = [vp]
     lib.cnf_comm_init.argtypes = [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int]
     lib.cnf_comm_init_all.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_int)]

@@ -37,11 +37,11 @@ def make_opt_callback(n: int) -> Callable[[int, float], bool]:
     return opt_callback
 
 
-def _matrix(X, device) -> torch.Tensor:
-    """permutedims(matrix(X)) as a Float32 device tensor: (n_features, n_samples)."""
+def _matrix(X, device, dtype=torch.float32) -> torch.Tensor:
+    """permutedims(matrix(X)) as a device tensor of the flow's data_type: (n_features, n_samples)."""
     if hasattr(X, "to_numpy"):          # pandas DataFrame / Series
         X = X.to_numpy()
-    t = torch.as_tensor(X, dtype=torch.float32)
+    t = torch.as_tensor(X, dtype=dtype)
     if t.dim() == 1:
         t = t[:, None]
     if t.dim() != 2:
@@ -140,11 +140,12 @@ class ICNFModel(_MLJICNF):
     """MLJ model of an unconditioned flow (src/exts/mlj_ext/core_icnf.jl)."""
 
     def fit(self, X, verbosity: int = 0):
+        _icnf._f64_refuse(self.icnf, "ICNFModel.fit (training)")
         return self._fit(_matrix(X, self.icnf.device), None)
 
     def transform(self, fitresult, Xnew):
         ps, st = fitresult
-        logp = _icnf.inference(self.icnf, TestMode(), _matrix(Xnew, self.icnf.device), ps, st)[0]
+        logp = _icnf.inference(self.icnf, TestMode(), _matrix(Xnew, self.icnf.device, self.icnf.data_type), ps, st)[0]
         return self._px(logp)
 
 
@@ -154,6 +155,7 @@ class CondICNFModel(_MLJICNF):
 
     def fit(self, XY, verbosity: int = 0):
         X, Y = XY
+        _icnf._f64_refuse(self.icnf, "CondICNFModel.fit (training)")
         x, y = _matrix(X, self.icnf.device), _matrix(Y, self.icnf.device)
         if x.shape[1] != y.shape[1]:
             raise ValueError("DimensionMismatch: X and Y need the same number of rows")
@@ -163,7 +165,8 @@ class CondICNFModel(_MLJICNF):
         Xnew, Ynew = XYnew
         ps, st = fitresult
         dev = self.icnf.device
-        logp = _icnf.inference(self.icnf, TestMode(), _matrix(Xnew, dev), _matrix(Ynew, dev), ps, st)[0]
+        dt = self.icnf.data_type
+        logp = _icnf.inference(self.icnf, TestMode(), _matrix(Xnew, dev, dt), _matrix(Ynew, dev, dt), ps, st)[0]
         return self._px(logp)
 
 
@@ -187,7 +190,13 @@ class ICNFDist:
         return ()
 
     def logpdf(self, A) -> torch.Tensor:
-        A = torch.as_tensor(A, dtype=torch.float32)
+        # a Float64 flow takes a tensor as it is (one of another precision is a TypeError in `inference`, not a cast)
+        if self.icnf.f64 and isinstance(A, torch.Tensor):
+            if A.dtype != torch.float64:
+                raise _icnf._DTypeMismatch(f"logpdf: the argument is {A.dtype} but the flow was built with data_type=torch.float64: "
+                                           "convert it explicitly (nothing is cast silently), or use a Float32 flow")
+        else:
+            A = torch.as_tensor(A, dtype=self.icnf.data_type)
         vec = A.dim() == 1                   # a single point: computed as a one-column matrix (core_icnf.jl:21-27)
         if vec:
             A = A[:, None]
@@ -210,7 +219,8 @@ class CondICNFDist(ICNFDist):
 
     def __init__(self, icnf: ICNF, mode: Mode, ys, ps: torch.Tensor, st: dict):
         super().__init__(icnf, mode, ps, st)
-        ys = torch.as_tensor(ys, dtype=torch.float32)
+        if not (icnf.f64 and isinstance(ys, torch.Tensor)):
+            ys = torch.as_tensor(ys, dtype=icnf.data_type)
         self.ys = (ys[:, None] if ys.dim() == 1 else ys).to(icnf.device)
 
     def _cond(self, n: int) -> tuple:

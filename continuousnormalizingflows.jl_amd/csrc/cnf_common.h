@@ -13,41 +13,51 @@ namespace cnf {
 // Fixed-step explicit Runge-Kutta tableaux, rounded to float (OrdinaryDiffEq converts its
 // tableau to T = Float32).  Values: SURVEY.md §8 A4 (Tsitouras 2011); classic RK4.
 // ---------------------------------------------------------------------------------------
-struct Tableau {
+// One table of decimal literals serves both precisions: TableauT<float> = Tableau (what the f32 kernels have always received:
+// every literal rounded once to float) and TableauT<double> = TableauD for the double-precision path (cnf_f64.hip), whose
+// coefficients never pass through float.
+template <class Real>
+struct TableauT {
     int ns;          // stage evaluations per step
-    float c[6];
-    float a[6][6];   // a[i][j], j < i
-    float b[6];
+    Real c[6];
+    Real a[6][6];    // a[i][j], j < i
+    Real b[6];
 };
+using Tableau = TableauT<float>;
+using TableauD = TableauT<double>;
 
-inline Tableau make_tableau(int alg) {
-    Tableau T{};
+template <class Real>
+inline TableauT<Real> make_tableau_as(int alg) {
+    TableauT<Real> T{};
+    auto r = [](double v) { return (Real)v; };
     if (alg == CNF_ALG_RK4) {
         T.ns = 4;
-        const float c[4] = {0.f, 0.5f, 0.5f, 1.f};
-        const float b[4] = {1.f / 6.f, 1.f / 3.f, 1.f / 3.f, 1.f / 6.f};
+        const Real c[4] = {r(0.0), r(0.5), r(0.5), r(1.0)};
+        const Real b[4] = {r(1.0) / r(6.0), r(1.0) / r(3.0), r(1.0) / r(3.0), r(1.0) / r(6.0)};
         for (int i = 0; i < 4; ++i) { T.c[i] = c[i]; T.b[i] = b[i]; }
-        T.a[1][0] = 0.5f;
-        T.a[2][1] = 0.5f;
-        T.a[3][2] = 1.f;
+        T.a[1][0] = r(0.5);
+        T.a[2][1] = r(0.5);
+        T.a[3][2] = r(1.0);
     } else {
         T.ns = 6;
-        const float c[6] = {0.f, 0.161f, 0.327f, 0.9f, 0.9800255409045097f, 1.f};
-        const float b[6] = {0.09646076681806523f, 0.01f, 0.4798896504144996f,
-                            1.379008574103742f, -3.290069515436081f, 2.324710524099774f};
+        const Real c[6] = {r(0.0), r(0.161), r(0.327), r(0.9), r(0.9800255409045097), r(1.0)};
+        const Real b[6] = {r(0.09646076681806523), r(0.01), r(0.4798896504144996),
+                           r(1.379008574103742), r(-3.290069515436081), r(2.324710524099774)};
         for (int i = 0; i < 6; ++i) { T.c[i] = c[i]; T.b[i] = b[i]; }
-        T.a[1][0] = 0.161f;
-        T.a[2][0] = -0.008480655492356989f; T.a[2][1] = 0.335480655492357f;
-        T.a[3][0] = 2.8971530571054935f;    T.a[3][1] = -6.359448489975075f;
-        T.a[3][2] = 4.3622954328695815f;
-        T.a[4][0] = 5.325864828439257f;     T.a[4][1] = -11.748883564062828f;
-        T.a[4][2] = 7.4955393428898365f;    T.a[4][3] = -0.09249506636175525f;
-        T.a[5][0] = 5.86145544294642f;      T.a[5][1] = -12.92096931784711f;
-        T.a[5][2] = 8.159367898576159f;     T.a[5][3] = -0.071584973281401f;
-        T.a[5][4] = -0.028269050394068383f;
+        T.a[1][0] = r(0.161);
+        T.a[2][0] = r(-0.008480655492356989); T.a[2][1] = r(0.335480655492357);
+        T.a[3][0] = r(2.8971530571054935);    T.a[3][1] = r(-6.359448489975075);
+        T.a[3][2] = r(4.3622954328695815);
+        T.a[4][0] = r(5.325864828439257);     T.a[4][1] = r(-11.748883564062828);
+        T.a[4][2] = r(7.4955393428898365);    T.a[4][3] = r(-0.09249506636175525);
+        T.a[5][0] = r(5.86145544294642);      T.a[5][1] = r(-12.92096931784711);
+        T.a[5][2] = r(8.159367898576159);     T.a[5][3] = r(-0.071584973281401);
+        T.a[5][4] = r(-0.028269050394068383);
     }
     return T;
 }
+inline Tableau make_tableau(int alg) { return make_tableau_as<float>(alg); }
+inline TableauD make_tableau_f64(int alg) { return make_tableau_as<double>(alg); }
 
 // ---------------------------------------------------------------------------------------
 // Activations.  act_fwd returns h = act(a) and writes d = act'(a).

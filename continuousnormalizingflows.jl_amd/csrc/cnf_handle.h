@@ -124,6 +124,12 @@ struct HandleAdaptive {
     DevBuf<float> buf;                   // adaptive Tsit5 whole solve: two states + two derivative scratch vectors
     int64_t B = 0;                       // columns the allocation holds: the stride of its slots
 };
+// double-precision evaluation path (cnf_api_f64.hip): a second parameter binding, independent of HandleParams
+struct HandleF64 {
+    bool have = false;
+    DevBuf<double> lux;                  // Lux-layout vector as handed to cnf_set_params_f64
+    DevBuf<double> image;                // W, bias and W^T of every layer, zero-padded (cnf_f64.h: F64Layer)
+};
 
 }  // namespace cnf
 
@@ -142,6 +148,7 @@ struct cnf_handle {
     cnf::HandleEmbedded emb;
     cnf::HandleVcabm vc;
     cnf::HandleAdaptive adp;
+    cnf::HandleF64 f64;
     // Hutchinson JVP mode without the Jacobian regulariser: eps^T (J eps) and (eps^T J) eps are the same number, so the loss is the
     // VJP mode's loss and its parameter gradient is served by the VJP mode's fused reverse sweeps through this internal handle of
     // the same configuration with mode = CNF_MODE_HUTCH_VJP (the JVP-specific gradient kernels are layer-wise only).

@@ -224,6 +224,11 @@ class VCABM:
 # ---------------------------------------------------------------------------------------
 # ICNF
 # ---------------------------------------------------------------------------------------
+class _DTypeMismatch(TypeError, ValueError):
+    """A tensor whose precision is not the flow's data_type.  A TypeError; also a ValueError, which is what a non-Float32 `ps`
+    raised before Float64 flows existed."""
+
+
 class _Handle:
     """Owns one cnf_handle (one trace mode / regulariser combination)."""
 
@@ -254,7 +259,13 @@ class ICNF:
       * `nn` must be a Chain of Dense layers with identity/tanh/softplus/sigmoid/swish/elu/gelu activations
         (elu with alpha = 1, gelu in its tanh form).  Nets with sigmoid, swish, elu or gelu hidden layers run
         layer-wise (or thread-per-sample for layers wider than 512): the fused kernels are built for tanh and softplus.
-      * data_type is Float32.
+      * data_type is Float32 (every entry point) or Float64.  A Float64 flow evaluates - augmented_f, inference, generate, loss,
+        logpdf / rand - with fixed-step Tsit5() / RK4() (adaptive=False and nsteps or dt) on the double-precision kernel
+        (csrc/cnf_f64.hip), takes and returns float64 tensors and casts nothing silently; adaptive stepping, VCABM, gradients and
+        fit are Float32 only and raise NotImplementedError on a Float64 flow.  Its `nsteps` form keeps t0 and t1 in double;
+        its `dt` form steps on the plan of the Float32 entries (fixed_dt_grid), which is made from the FLOAT32 values of t0, t1
+        and dt: dt=0.3 steps by 0.30000001192..., and an end point a Float32 cannot hold moves by up to 6e-8 relative.  Give
+        `nsteps` where the span must be exact in double.
     """
 
     def __init__(self, *, data_type=torch.float32, compute_mode: Optional[ComputeMode] = None,
@@ -271,9 +282,10 @@ class ICNF:
         lambda3 = aliases.pop("λ₃", lambda3)
         if aliases:
             raise TypeError(f"MethodError: unknown keyword(s) {sorted(aliases)}")
-        if data_type is not torch.float32:
-            raise TypeError("MethodError: the HIP path computes in Float32 only")
+        if data_type is not torch.float32 and data_type is not torch.float64:
+            raise TypeError("MethodError: the HIP path computes in Float32 or Float64")
         self.data_type = data_type
+        self.f64 = data_type is torch.float64
         self.compute_mode = compute_mode if compute_mode is not None else HIPVecJacMatrixMode()
         if not isinstance(self.compute_mode, MatrixMode):
             raise TypeError("MethodError: only MatrixMode compute modes are implemented "
@@ -469,13 +481,18 @@ class ICNF:
             cfg.kernel_path = self.compute_mode.kernel_path
             cfg.arith = arith
             h = _Handle(cfg)
+            if self.f64 and not h.lib.cnf_f64_supported(h.ptr):   # JVP modes, flows past the LDS limit: the library's own reason
+                raise _lib.CnfError(_lib.ERR_UNSUPPORTED, h.lib.cnf_last_error().decode() + " (data_type=torch.float32 runs it in Float32)")
             self._handles[key] = h
         return h
 
     def _bind_params(self, h: _Handle, ps: torch.Tensor):
         w_off, b_off, n = self.nn.param_offsets()
-        if ps.dtype != torch.float32 or ps.dim() != 1 or ps.numel() != n:
-            raise ValueError(f"DimensionMismatch: ps must be a Float32 vector of length {n}")
+        if ps.dtype != self.data_type and ps.dtype in (torch.float32, torch.float64):
+            raise _DTypeMismatch(f"ps is {ps.dtype} but the flow was built with data_type={self.data_type}: nothing is cast "
+                                 f"silently (DimensionMismatch: ps must be a {'Float64' if self.f64 else 'Float32'} vector of length {n})")
+        if ps.dtype != self.data_type or ps.dim() != 1 or ps.numel() != n:
+            raise ValueError(f"DimensionMismatch: ps must be a {'Float64' if self.f64 else 'Float32'} vector of length {n}")
         if ps.is_cuda and ps.device != self.device:
             raise ValueError(f"ps lives on {ps.device} but this ICNF is bound to {self.device}")
         # skip the repack only for the SAME tensor object at the same version: a data_ptr alone can be a freed
@@ -487,8 +504,8 @@ class ICNF:
         ps_c = self.nn.abi_params(ps).contiguous()
         wo = (C.c_size_t * len(w_off))(*w_off)
         bo = (C.c_size_t * len(b_off))(*b_off)
-        _lib.check(h.lib.cnf_set_params(h.ptr, _ptr(ps_c), ps_c.numel(), wo, bo, int(ps_c.is_cuda),
-                                        _stream_ptr(self.device)))
+        set_params = h.lib.cnf_set_params_f64 if self.f64 else h.lib.cnf_set_params   # two independent bindings of the handle
+        _lib.check(set_params(h.ptr, _ptr(ps_c), ps_c.numel(), wo, bo, int(ps_c.is_cuda), _stream_ptr(self.device)))
         h.params_key = key
         h.params_ref = weakref.ref(ps)
 
@@ -545,44 +562,45 @@ class ICNF:
 # helpers
 # ---------------------------------------------------------------------------------------
 def setup(rng: Optional[torch.Generator], icnf: ICNF):
-    """LuxCore.setup + ComponentArray: flat Float32 parameter vector (glorot-uniform weights,
-    zero biases — Lux.Dense defaults) and an empty state."""
+    """LuxCore.setup + ComponentArray: flat parameter vector of the flow's data_type (glorot-uniform weights,
+    zero biases — Lux.Dense defaults; drawn in float64 either way, so a Float32 flow's vector is the rounded Float64 one)
+    and an empty state."""
     if icnf.nn.planar is not None:   # (u, w, b): glorot-uniform vectors, zero bias (planar_layer.jl:36-50)
         pl = icnf.nn.planar
         u = (torch.rand(pl.n_out, generator=rng, dtype=torch.float64) * 2 - 1) * math.sqrt(6.0 / (pl.n_out + 1))
         w = (torch.rand(pl.n_in, generator=rng, dtype=torch.float64) * 2 - 1) * math.sqrt(6.0 / (pl.n_in + 1))
         b = torch.zeros(1 if pl.use_bias else 0, dtype=torch.float64)
-        return torch.cat([u, w, b]).to(torch.float32), {}
+        return torch.cat([u, w, b]).to(icnf.data_type), {}
     parts = []
     for l in icnf.nn.layers:
         lim = math.sqrt(6.0 / (l.n_in + l.n_out))
         W = (torch.rand(l.n_out, l.n_in, generator=rng, dtype=torch.float64) * 2 - 1) * lim
         parts.append(W.t().reshape(-1))  # column-major (out x in)
         parts.append(torch.zeros(l.n_out, dtype=torch.float64))
-    return torch.cat(parts).to(torch.float32), {}
+    return torch.cat(parts).to(icnf.data_type), {}
 
 
-def _colmajor(a: torch.Tensor, rows: int, name: str, device) -> torch.Tensor:
+def _colmajor(a: torch.Tensor, rows: int, name: str, device, dtype=torch.float32) -> torch.Tensor:
     """(rows, B) tensor -> Julia memory layout (B x rows contiguous), on the device."""
     if a.dim() != 2 or a.shape[0] != rows:
         raise ValueError(f"DimensionMismatch: {name} must be ({rows}, B), got {tuple(a.shape)}")
     if a.device != device:
         raise ValueError(f"{name} must live on {device} (got {a.device})")
-    return a.to(torch.float32).t().contiguous()
+    return a.to(dtype).t().contiguous()
 
 
 def _draw_eps(icnf: ICNF, K: int, B: int) -> torch.Tensor:
     """rand!(rng, epsdist, eps) (src/core/base_icnf.jl:258-259): standard normal unless icnf.epsdist says otherwise."""
     shape = (B, K * icnf.D)
     if icnf.epsdist is None:
-        return torch.randn(shape, generator=icnf.rng, device=icnf.device, dtype=torch.float32)
+        return torch.randn(shape, generator=icnf.rng, device=icnf.device, dtype=icnf.data_type)
     if icnf.epsdist == "rademacher":
         r = torch.randint(0, 2, shape, generator=icnf.rng, device=icnf.device)
-        return (2 * r - 1).to(torch.float32)
+        return (2 * r - 1).to(icnf.data_type)
     e = icnf.epsdist(icnf.rng, shape, icnf.device)
     if tuple(e.shape) != shape:
         raise ValueError(f"DimensionMismatch: epsdist must return a {shape} tensor")
-    return e.to(device=icnf.device, dtype=torch.float32).contiguous()
+    return e.to(device=icnf.device, dtype=icnf.data_type).contiguous()
 
 
 def _split_args(icnf: ICNF, args, what: str):
@@ -595,6 +613,148 @@ def _split_args(icnf: ICNF, args, what: str):
     if len(args) != 3:
         raise TypeError(f"MethodError: {what}(icnf, mode, xs, ps, st) expected")
     return args[0], None, args[1], args[2]
+
+
+# ---------------------------------------------------------------------------------------
+# Float64 flows (ICNF(data_type=torch.float64)): the evaluation path on cnf_*_f64 (csrc/cnf_f64.hip)
+# ---------------------------------------------------------------------------------------
+def _f64_refuse(icnf: ICNF, what: str) -> None:
+    """What a Float64 flow does not do, refused on the arguments alone (before any library call)."""
+    if icnf.f64:
+        raise NotImplementedError(f"{what} is not implemented for data_type=Float64 (the double-precision path evaluates: "
+                                  "augmented_f, inference, generate, loss, logpdf, rand); build the flow with "
+                                  "data_type=torch.float32 to use it in Float32")
+
+
+def _f64_check(icnf: ICNF, what: str, differentiable: bool = False) -> int:
+    """The solver of a Float64 call (its alg id), or the refusal - before any library call."""
+    if differentiable:
+        _f64_refuse(icnf, f"{what}(differentiable=True)")
+    kw = icnf.sol_kwargs
+    alg = kw.get("alg")
+    if alg is None or getattr(alg, "alg_id", None) == _lib.ALG_VCABM or kw.get("adaptive", True):
+        raise NotImplementedError(f"{what}: a Float64 flow runs fixed-step solves only - sol_kwargs=dict(alg=Tsit5() or RK4(), "
+                                  "adaptive=False, nsteps=... or dt=...); adaptive stepping and VCABM() (the default alg) are "
+                                  "implemented in Float32 (data_type=torch.float32)")
+    return icnf._solver()
+
+
+def _f64_cols(icnf: ICNF, a: torch.Tensor, rows: int, name: str) -> torch.Tensor:
+    """_colmajor for a Float64 flow: a tensor of another precision is a TypeError, never a cast."""
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+        raise _DTypeMismatch(f"{name} is {getattr(a, 'dtype', type(a).__name__)} but the flow was built with "
+                             "data_type=torch.float64: convert it explicitly (nothing is cast silently), or use a Float32 flow")
+    return _colmajor(a, rows, name, icnf.device, torch.float64)
+
+
+def _f64_ps(icnf: ICNF, ps) -> None:
+    """The precision of `ps`, checked on the arguments alone (ICNF._bind_params checks it again with the shape)."""
+    if not isinstance(ps, torch.Tensor) or ps.dtype != torch.float64:
+        raise _DTypeMismatch(f"ps is {getattr(ps, 'dtype', type(ps).__name__)} but the flow was built with data_type=torch.float64: "
+                             "convert it explicitly (nothing is cast silently), or use a Float32 flow")
+
+
+def _f64_inputs(icnf: ICNF, mode: Mode, B: int, eps, ys):
+    """(eps, ys) of a call of B columns, column-major: the probes drawn in double unless given."""
+    K = icnf.nprobes if isinstance(mode, TrainMode) else 1
+    if eps is None:
+        e = _draw_eps(icnf, K, B)
+    else:
+        e = _f64_cols(icnf, eps, K * icnf.D, "eps")
+        if e.shape[0] != B:
+            raise ValueError("DimensionMismatch: eps must have B columns")
+    y = _f64_cols(icnf, ys, icnf.nconditions, "ys") if icnf.conditioned else None
+    if y is not None and y.shape[0] != B:
+        raise ValueError("DimensionMismatch: xs and ys must have the same number of columns")
+    return e, y
+
+
+def _f64_spans(icnf: ICNF, t0: float, t1: float):
+    """The solve from t0 to t1 as [(ta, tb, nsteps)] calls of equal steps: one, or - `dt` with a shorter last step - the full
+    steps and the tail of the plan fixed_dt_grid computes.  That plan is made from the Float32 values of dt, t0 and t1 (one plan
+    for both precisions, and the one the oracle's fixed_dt_grid makes), so this form carries Float32 times; `nsteps` does not."""
+    dt = icnf._fixed_dt()
+    if dt is None:
+        return [(t0, t1, icnf._nsteps(t0, t1))]
+    ts = icnf.fixed_dt_grid(t0, t1, dt)
+    if len(ts) < 2:
+        return []
+    if len(ts) >= 3 and abs(abs(ts[-1] - ts[-2]) - abs(ts[1] - ts[0])) > 1e-7 * abs(t1 - t0):
+        return [(ts[0], ts[-2], len(ts) - 2), (ts[-2], ts[-1], 1)]
+    return [(ts[0], ts[-1], len(ts) - 1)]
+
+
+def _f64_integrate(icnf: ICNF, h: _Handle, alg: int, u0c: torch.Tensor, e, y, t0: float, t1: float, sp) -> torch.Tensor:
+    """cnf_integrate_fixed_f64 over the spans of the plan; (B, S) column-major in and out."""
+    B = u0c.shape[0]
+    u1 = u0c.clone()
+    for ta, tb, n in _f64_spans(icnf, t0, t1):
+        _lib.check(h.lib.cnf_integrate_fixed_f64(h.ptr, alg, n, ta, tb, _ptr(u1), _ptr(e), _ptr(y), B, _ptr(u1), sp))   # in place
+    return u1
+
+
+def _inference_f64(icnf: ICNF, mode: Mode, alg: int, xs, ys, ps, eps, return_state: bool, raw: bool):
+    _f64_ps(icnf, ps)
+    x = _f64_cols(icnf, xs, icnf.nvariables, "xs")
+    h = icnf._handle(mode)
+    icnf._bind_params(h, ps)
+    dev, D, nv, B = icnf.device, icnf.D, icnf.nvariables, x.shape[0]
+    e, y = _f64_inputs(icnf, mode, B, eps, ys)
+    t0, t1 = icnf._steer_tspan(mode)
+    sp = _stream_ptr(dev)
+    spans = _f64_spans(icnf, t0, t1)
+    if len(spans) == 1:
+        ta, tb, n = spans[0]
+        logp = torch.empty(B, device=dev, dtype=torch.float64)
+        regs = torch.empty(3, B, device=dev, dtype=torch.float64)
+        uf = torch.empty(B, icnf.S, device=dev, dtype=torch.float64) if (return_state or icnf.basedist is not None) else None
+        _lib.check(h.lib.cnf_inference_fixed_f64(h.ptr, alg, n, ta, tb, _ptr(x), _ptr(e), _ptr(y), B, _ptr(logp), _ptr(regs), _ptr(uf), sp))
+    else:   # full steps + tail (or an empty span): the state between the calls, the epilogue in torch float64
+        u0 = torch.cat([x, torch.zeros(B, icnf.S - nv, device=dev, dtype=torch.float64)], dim=1)
+        uf = _f64_integrate(icnf, h, alg, u0, e, y, t0, t1, sp)
+        z = uf[:, :D]
+        logp = -0.5 * (z * z).sum(dim=1) - 0.5 * D * math.log(2.0 * math.pi) - uf[:, D]
+        reg = isinstance(mode, TrainMode) and mode.reg
+        A = torch.sqrt((z[:, nv:] * z[:, nv:]).sum(dim=1)) if (reg and icnf.lambda3 != 0.0 and icnf.augmented) else torch.zeros_like(logp)
+        regs = torch.stack([uf[:, D + 1], uf[:, D + 2], A])
+    if icnf.basedist is not None:
+        logp = icnf.basedist.log_prob(uf[:, :D]).to(torch.float64) - uf[:, D]
+    if raw:
+        return logp, regs
+    out = (logp, (regs[0], regs[1], regs[2]))
+    return out + (uf.t(),) if return_state else out
+
+
+def _generate_f64(icnf: ICNF, mode: Mode, alg: int, ys, ps, n: int, z0, eps):
+    dev, D, S = icnf.device, icnf.D, icnf.S
+    _f64_ps(icnf, ps)
+    if z0 is not None:
+        z = _f64_cols(icnf, z0, D, "z0")
+    h = icnf._handle(mode)
+    icnf._bind_params(h, ps)
+    if z0 is None and icnf.basedist is not None:
+        z = icnf.basedist.sample((n,)).to(device=dev, dtype=torch.float64).reshape(n, D)
+    elif z0 is None:
+        z = torch.randn(n, D, generator=icnf.rng, device=dev, dtype=torch.float64)
+    e, y = _f64_inputs(icnf, mode, n, eps, ys)
+    u0 = torch.zeros(n, S, device=dev, dtype=torch.float64)
+    u0[:, :D] = z
+    t0, t1 = icnf._steer_tspan(mode)
+    u1 = _f64_integrate(icnf, h, alg, u0, e, y, t1, t0, _stream_ptr(dev))
+    return u1[:, :icnf.nvariables].t()
+
+
+def _augmented_f_f64(icnf: ICNF, mode: Mode, u, ps, t: float, eps, ys):
+    _f64_ps(icnf, ps)
+    um = _f64_cols(icnf, u, icnf.S, "u")
+    h = icnf._handle(mode)
+    icnf._bind_params(h, ps)
+    K = icnf.nprobes if isinstance(mode, TrainMode) else 1
+    e = None if eps is None else _f64_cols(icnf, eps, K * icnf.D, "eps")
+    y = _f64_cols(icnf, ys, icnf.nconditions, "ys") if icnf.conditioned else None
+    du = torch.empty_like(um)
+    _lib.check(h.lib.cnf_aug_f_f64(h.ptr, _ptr(du), _ptr(um), float(t), _ptr(e), _ptr(y), um.shape[0], _stream_ptr(icnf.device)))
+    return du.t()
 
 
 # ---------------------------------------------------------------------------------------
@@ -649,6 +809,7 @@ def integrate_vjp(icnf: ICNF, mode: Mode, u0: torch.Tensor, ps: torch.Tensor, u1
     A shard's `grad_ps` is the partial sum over its columns.
     `want_ys_bar=True` (conditioned flows): `(grad_ps, u0_bar, ys_bar, u1)` with `ys_bar = u1_bar^T du1/dys` ((nconditions, B)),
     the cotangent of the conditions - per column, so a shard's `ys_bar` is complete for its columns."""
+    _f64_refuse(icnf, "integrate_vjp (the pullback of the solve)")
     if want_ys_bar and not icnf.conditioned:
         raise ValueError("integrate_vjp(want_ys_bar=True): the flow has no conditions (nconditions = 0)")
     if icnf._solver() == _lib.ALG_VCABM:
@@ -817,6 +978,8 @@ def inference(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None,
     partial sum of its own columns (the gradient of `ys` is per column)."""
     xs, ys, ps, st = _split_args(icnf, args, "inference")
     _check_cond_grad(icnf, differentiable, cond_grad, "inference")
+    if icnf.f64:
+        return _inference_f64(icnf, mode, _f64_check(icnf, "inference", differentiable), xs, ys, ps, eps, return_state, _raw)
     group = icnf._group(group)
     if differentiable:
         return _inference_differentiable(icnf, mode, xs, ys, ps, eps, return_state, group, cond_grad)
@@ -884,6 +1047,8 @@ def generate(icnf: ICNF, mode: Mode, *args, z0: Optional[torch.Tensor] = None,
             raise TypeError("MethodError: generate(icnf, mode, ps, st, n) expected")
         ps, st, n = args
         ys = None
+    if icnf.f64:
+        return _generate_f64(icnf, mode, _f64_check(icnf, "generate", differentiable), ys, ps, n, z0, eps)
     if differentiable:
         _check_differentiable(icnf, ys, "generate", cond_grad)
     h = icnf._handle(mode)
@@ -927,6 +1092,8 @@ def augmented_f(icnf: ICNF, mode: Mode, u: torch.Tensor, ps: torch.Tensor, t: fl
                 eps: Optional[torch.Tensor], ys: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One dynamics call du = f(u, p, t): the closure of make_ode_func
     (src/core/base_icnf.jl:62-78; src/core/icnf.jl:517-536).  u: (S, B)."""
+    if icnf.f64:
+        return _augmented_f_f64(icnf, mode, u, ps, t, eps, ys)
     h = icnf._handle(mode)
     icnf._bind_params(h, ps)
     dev = icnf.device
@@ -1026,6 +1193,12 @@ def loss(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor] = None, grou
     from .sharding import reduce_loss
     group = icnf._group(group)
     from .sharding import is_sharded
+    if icnf.f64:   # the mean in torch float64; a sharded mean in double is not provided
+        _f64_check(icnf, "loss")
+        if is_sharded(group):
+            _f64_refuse(icnf, "loss over column shards")
+        logp, regs = inference(icnf, mode, *args, eps=eps, _raw=True)
+        return (-logp + icnf.lambda1 * regs[0] + icnf.lambda2 * regs[1] + icnf.lambda3 * regs[2]).mean()
     sp = _stream_ptr(icnf.device)
     if (icnf.adaptive and not is_sharded(group) and icnf.basedist is None and getattr(icnf, "adaptive_policy", "library") == "library"):
         out = _loss_adaptive_one_call(icnf, mode, args, eps, sp)
@@ -1056,6 +1229,7 @@ def loss_and_gradient(icnf: ICNF, mode: Mode, *args, eps: Optional[torch.Tensor]
     to the solver tolerance (tests/test_parity_gpu.py bounds the difference); the reference's own gradient
     (QuadratureAdjoint, icnf.jl:90-99) is likewise a separate solve that matches its forward pass to tolerance."""
     from .sharding import global_count, is_sharded, reduce_gradient, reduce_loss
+    _f64_refuse(icnf, "loss_and_gradient")
     group = icnf._group(group)
     xs, ys, ps, st = _split_args(icnf, args, "loss_and_gradient")
     if icnf.basedist is not None:

@@ -34,6 +34,7 @@
  *   training                 cnf_loss_grad_fixed, cnf_loss_grad_grid, cnf_loss_grad_adaptive  (dloss/dps, optionally dloss/dxs)
  *   pullback of the solve    cnf_integrate_fixed_vjp, cnf_integrate_grid_vjp  (any cotangent of the final state -> dps, du0)
  *                            cnf_integrate_fixed_vjp_cond, cnf_integrate_grid_vjp_cond  (conditioned flows: dys as well)
+ *   Float64 flows            cnf_f64_supported, cnf_set_params_f64, cnf_aug_f_f64, cnf_integrate_fixed_f64, cnf_inference_fixed_f64
  *   column shards (RCCL)     cnf_comm_unique_id, cnf_comm_init, cnf_comm_init_all, cnf_comm_destroy, cnf_comm_rank, cnf_comm_size,
  *                            cnf_allreduce_loss (the mean in `loss`), cnf_allreduce_sum, cnf_comm_group_start / _end
  *   tuning (A/B, tests)      cnf_get_tuning, cnf_set_tuning
@@ -481,6 +482,34 @@ int cnf_integrate_grid_vjp_cond(cnf_handle* h, int alg, int nsteps, const float*
 /* Which implementation such a call takes (with or without ys_bar): 1 fused per-wave sweep, 2 layer-wise, 0 none (the call returns
  * CNF_ERR_UNSUPPORTED). */
 int cnf_vjp_path_for(const cnf_handle* h, int64_t B, int alg, int on_grid);
+
+/* ---- Float64 flows: the reference's ICNF(; data_type = Float64) (src/core/icnf.jl:54) -------------------------------------
+ * The evaluation path in double precision: dynamics call, fixed-step solve, inference.  One kernel (csrc/cnf_f64.hip) with
+ * run-time shapes, every product of the chain on v_mfma_f64_16x16x4_f64, a wave per 16-sample tile for the whole solve; the
+ * tableau coefficients, the step and the stage times t0 + n dt + c_i dt are doubles.  Shapes, row order and NULL conventions
+ * are those of the Float32 twins (cnf_aug_f, cnf_integrate_fixed, cnf_inference_fixed) with every array in double.
+ *   modes        CNF_MODE_HUTCH_VJP with nprobes >= 1, and CNF_MODE_EXACT (the D unit vectors through the same pullback);
+ *                CNF_MODE_HUTCH_JVP is refused with CNF_ERR_UNSUPPORTED
+ *   flows        any Dense chain of the handle (conditions, autonomous, naug, the three regularisers, all seven activations)
+ *                whose per-wave working set fits the 160 KB of LDS of a compute unit:
+ *                128 bytes x (pad4(n_in) + sum_l pad16(out_l) + 2 max_l pad16(width_l) + 7 (D + 3) + K D) <= 163840
+ *                (K D = 0 in EXACT mode).  cnf_f64_supported returns 1 or 0, with the reason for a 0 in cnf_last_error.
+ *   parameters   cnf_set_params_f64 is a second binding of the handle, independent of cnf_set_params: a double vector in the
+ *                same Lux layout, copied and repacked once per call (enqueued on `stream`); the Float32 binding is untouched
+ *                and neither is needed for the other.  An f64 entry without it returns CNF_ERR_NO_PARAMS.
+ *   solvers      CNF_ALG_RK4, CNF_ALG_TSIT5 on nsteps equal steps; t1 < t0 integrates backwards; u1 may alias u0.
+ * Stream-ordered like the twins, no host synchronisation (a HOST p is copied before cnf_set_params_f64 returns).  A column's
+ * result does not depend on which other columns are in the call.  Gradients, adaptive solves and column-shard reductions in
+ * double are not provided. */
+int cnf_f64_supported(const cnf_handle* h);
+int cnf_set_params_f64(cnf_handle* h, const double* p, size_t n, const size_t* w_off, const size_t* b_off, int p_is_device,
+                       void* stream);
+int cnf_aug_f_f64(cnf_handle* h, double* du, const double* u, double t, const double* eps, const double* ys, int64_t B,
+                  void* stream);
+int cnf_integrate_fixed_f64(cnf_handle* h, int alg, int nsteps, double t0, double t1, const double* u0, const double* eps,
+                            const double* ys, int64_t B, double* u1, void* stream);
+int cnf_inference_fixed_f64(cnf_handle* h, int alg, int nsteps, double t0, double t1, const double* x, const double* eps,
+                            const double* ys, int64_t B, double* logp, double* regs, double* u_final, void* stream);
 
 /* ---- column shards: the one exchange step of the path -----------------------------------------
  * Under fixed-step integration every column (sample) is independent (src/core/icnf.jl:530-535 is column-wise), so rank r
